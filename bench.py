@@ -17,6 +17,17 @@ is point-sharded over N ranks (strong scaling, RCCL all-reduce of the
 reduced camera system).
 
 Run:  python bench.py [--gpus N] [--steps K] [--warmup W] [--config cfg3]
+                       [--dump-outputs DIR] [--full]
+
+A plain run sets up, ramps the clock, warms up, times the K steps and prints
+the result line.  --full adds everything else the benchmark measures, each in
+runs of its own outside the timed steps: the per-phase / per-kernel HIP-event
+passes and the rooflines made from them, the CPU baselines, the config-5
+replay carried in the config-3 line and the growing replays' device-time
+replay.  --dump-outputs DIR writes what the last timed step computed as
+DIR/<name>.npy (float64); the scenes are seeded and the timed passes leave the
+parameters where they are, so two runs with the same arguments start every
+step from the same inputs.
 """
 from __future__ import annotations
 
@@ -59,9 +70,18 @@ def main():
                          "the GPU holds under load (DVFS: the first ~30 ms of passes run "
                          "slower whatever W is; recorded in the line as clock_ramp)")
     ap.add_argument("--config", default="cfg3")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need, in runs of "
+                         "their own: per-phase / per-kernel timing passes and rooflines, the "
+                         "CPU baselines, the config-5 replay in the cfg3 line, the growing "
+                         "replays' device-time replay")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed as "
+                         "DIR/<name>.npy (float64)")
+    ap.add_argument("--no-cpu-baseline", action="store_true",
+                    help="--full: without the CPU baselines")
     ap.add_argument("--no-other-configs", action="store_true",
-                    help="cfg3: skip the config-5 replay carried in the line")
+                    help="--full, cfg3: skip the config-5 replay carried in the line")
     ap.add_argument("--host-scene", action="store_true",
                     help="generate the banded configs with numpy instead of on the GPU")
     ap.add_argument("--cpu-sample-points", type=int, default=0,
@@ -156,25 +176,27 @@ def main():
         ramp["seconds"] += time.perf_counter() - t_r
         ramp["passes"] += 3 + n_ramp
     clock_ramp()
-    # per-phase and per-kernel device timing (HIP events around every launch on
-    # the library stream), in untimed passes after the clock ramp (at the
-    # steady-state clock, as the timed steps and rocprofv3's kernel trace see
-    # it: taken before the ramp they read the fused kernel ~8 % slow, 278 vs
-    # 258 us, profiles/r06/r06b_cfg3_kernel_stats.csv)
-    ba.set_timing(True)
-    ba.kernel_ms(reset=True)
-    phases = []
-    n_timed = max(1, min(10, args.steps))
-    for _ in range(n_timed):
-        ba.step(relinearize=True, update_lm=False)
-        phases.append(ba.phase_ms())
-    kms = ba.kernel_ms(reset=True)
-    ba.set_timing(False)
-    ph = {k: float(np.median([p[k] for p in phases])) for k in phases[0]}
-    # and the ramp again: the timing passes synchronise after every pass, the
-    # GPU idles between them and its clock drops (a 20-step region right
-    # after them ran 0.562 against 0.526 ms/pass)
-    clock_ramp()
+    ph = kms = None
+    if args.full:
+        # per-phase and per-kernel device timing (HIP events around every launch
+        # on the library stream), in untimed passes after the clock ramp (at the
+        # steady-state clock, as the timed steps and rocprofv3's kernel trace see
+        # it: taken before the ramp they read the fused kernel ~8 % slow, 278 vs
+        # 258 us, profiles/r06/r06b_cfg3_kernel_stats.csv)
+        ba.set_timing(True)
+        ba.kernel_ms(reset=True)
+        phases = []
+        n_timed = max(1, min(10, args.steps))
+        for _ in range(n_timed):
+            ba.step(relinearize=True, update_lm=False)
+            phases.append(ba.phase_ms())
+        kms = ba.kernel_ms(reset=True)
+        ba.set_timing(False)
+        ph = {k: float(np.median([p[k] for p in phases])) for k in phases[0]}
+        # and the ramp again: the timing passes synchronise after every pass, the
+        # GPU idles between them and its clock drops (a 20-step region right
+        # after them ran 0.562 against 0.526 ms/pass)
+        clock_ramp()
     for _ in range(args.warmup):
         ba.step(relinearize=True, update_lm=False)
     ba.sync()
@@ -200,32 +222,43 @@ def main():
         dt = float(tt.item())
     ms_step = 1e3 * dt / args.steps
     its = args.steps / dt
-    log(f"[bench] {ms_step:.3f} ms/iteration  phases(ms): " +
-        " ".join(f"{k}={v:.3f}" for k, v in ph.items()))
+    log(f"[bench] {ms_step:.3f} ms/iteration" + ("  phases(ms): " + " ".join(
+        f"{k}={v:.3f}" for k, v in ph.items()) if ph else ""))
     log(f"[bench] last pass: old_sse={info.old_sse:.9g} new_sse={info.new_sse:.9g} "
         f"rho={info.rho:.4g}")
+    if args.dump_outputs:
+        # what the caller of the last timed step holds: its info record, the
+        # step it solved for (vlgba_get_step) and the parameters (the bench's
+        # pass does not apply the step: they are the inputs, bit for bit)
+        da, db = ba.last_step()
+        a_out, b_out = ba.get_params()
+        dump_outputs(args.dump_outputs, rank, world, step_info=step_info_array(info),
+                     da=da, db=db, a=a_out, b=b_out)
 
     N = sc.num_obs
-    # ---- roofline of the dominant kernel -----------------------------------
     plan = ba.plan_info()
     log("[bench] plan: " + " ".join(f"{k}={v}" for k, v in plan.items()))
-    roofs = {k: kernel_roofline(k, tot, calls, plan, n_timed) for k, (tot, calls) in
-             kms.items()}
-    traffic, valu = pmc_traffic(args.config, plan)
-    for k, r in roofs.items():
-        r["traffic"] = traffic.get(k)
-        if k in valu:   # the VALU-issue roof beside the HBM / MFMA one
-            w = valu[k] / (r["avg_launch_us"] * 1e-6)
-            r["valu_issue"] = {"winst_per_launch": valu[k], "achieved": w,
-                               "peak": PEAK_VALU_WINST, "unit": "wave-instr/s",
-                               "frac": w / PEAK_VALU_WINST,
-                               "source": f"SQ_INSTS_VALU, profiles/pmc_traffic_{args.config}.json"}
-    dom = max(kms, key=lambda k: kms[k][0])
-    roof = roofs[dom]
-    log("[bench] kernels (avg us/launch, launches/pass, roofline frac): " +
-        "  ".join(f"{k}={1e3 * t / c:.1f}us x{c / n_timed:.0f} "
-                  f"{roofs[k]['frac']:.3f}" for k, (t, c) in
-                  sorted(kms.items(), key=lambda kv: -kv[1][0])))
+    roofs, roof = {}, None
+    if args.full:
+        # ---- roofline of the dominant kernel -------------------------------
+        roofs = {k: kernel_roofline(k, tot, calls, plan, n_timed) for k, (tot, calls) in
+                 kms.items()}
+        traffic, valu = pmc_traffic(args.config, plan)
+        for k, r in roofs.items():
+            r["traffic"] = traffic.get(k)
+            if k in valu:   # the VALU-issue roof beside the HBM / MFMA one
+                w = valu[k] / (r["avg_launch_us"] * 1e-6)
+                r["valu_issue"] = {"winst_per_launch": valu[k], "achieved": w,
+                                   "peak": PEAK_VALU_WINST, "unit": "wave-instr/s",
+                                   "frac": w / PEAK_VALU_WINST,
+                                   "source": "SQ_INSTS_VALU, "
+                                             f"profiles/pmc_traffic_{args.config}.json"}
+        dom = max(kms, key=lambda k: kms[k][0])
+        roof = roofs[dom]
+        log("[bench] kernels (avg us/launch, launches/pass, roofline frac): " +
+            "  ".join(f"{k}={1e3 * t / c:.1f}us x{c / n_timed:.0f} "
+                      f"{roofs[k]['frac']:.3f}" for k, (t, c) in
+                      sorted(kms.items(), key=lambda kv: -kv[1][0])))
 
     # the solve's fallbacks, outside the timed region: their count in the timed
     # passes, and one pass of each forced (vlgba_debug_force_status) -- the
@@ -249,7 +282,7 @@ def main():
         log(f"[bench] fallbacks: {fallbacks}")
 
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         cpu = cpu_baseline(sc, a0, b0, num_a, args.cpu_sample_points,
                            dense=args.config in ("cfg1", "cfg2"))
 
@@ -273,27 +306,29 @@ def main():
                                "fix_calibration (num_a=6), full LM pass per step, one "
                                "linearisation per step" + (
                                    " (fused into the update: k_update_linearize)"
-                                   if "k_update_linearize" in kms else ""),
+                                   if kms and "k_update_linearize" in kms else ""),
                    "cameras": sc.m, "points": sc.n, "observations": N,
                    "parallelism": f"point-shard x{world}",
                    "collective": "rccl" if comm_id is not None else
                                  ("gloo host all-reduce (ranks share a GPU)" if world > 1 else
                                   None)},
-        "phases_ms": ph,
         "clock_ramp": ramp,
-        "roofline": roof,
         "whole_pass": whole_pass(plan, ms_step),
-        "solve_roofline": {k: roofs[k] for k in SOLVE_FLOPS if k in roofs},
         "solve_fallbacks": fallbacks,
-        "cpu_baseline": cpu,
+        "full": args.full,
     }
+    if args.full:
+        out.update({"phases_ms": ph, "roofline": roof,
+                    "solve_roofline": {k: roofs[k] for k in SOLVE_FLOPS if k in roofs},
+                    "cpu_baseline": cpu})
     ba.close()
-    if rank == 0 and world == 1 and args.config == "cfg3" and not args.no_other_configs:
+    if (args.full and rank == 0 and world == 1 and args.config == "cfg3"
+            and not args.no_other_configs):
         # config 5 (the growing replay) measured in the same driver run: three
         # timed replays after one untimed, its CPU baseline beside it
         try:
             out["other_configs"] = {"cfg5": replay_summary(
-                replay_line("cfg5", 3, 1, not args.no_cpu_baseline))}
+                replay_line("cfg5", 3, 1, not args.no_cpu_baseline, True))}
         except Exception as e:   # noqa: BLE001 -- the cfg3 line stands on its own
             log(f"[bench] cfg5 replay failed: {e!r}")
             out["other_configs"] = {"cfg5": {"error": repr(e)}}
@@ -301,6 +336,28 @@ def main():
         print(json.dumps(out), flush=True)
     if world > 1:
         dist.destroy_process_group()
+
+
+def step_info_array(info):
+    """A pass's vlgba_step_info as a float64 vector: old_sse, new_sse, dpg, rho,
+    lambda, accepted, chol_failed, pinv, spin_retry, nd_retry."""
+    return np.array([info.old_sse, info.new_sse, info.dpg, info.rho, info.lambda_,
+                     info.accepted, info.chol_failed, info.pinv, info.spin_retry,
+                     info.nd_retry], dtype=np.float64)
+
+
+def dump_outputs(path, rank=0, world=1, **arrays):
+    """--dump-outputs: each array as DIR/<name>.npy, float64 (config 3's five
+    are 24 MB together).  With more than one rank every rank writes what it
+    holds, rank r > 0 as <name>.rank<r>.npy."""
+    os.makedirs(path, exist_ok=True)
+    total = 0
+    for name, arr in arrays.items():
+        arr = np.ascontiguousarray(arr, dtype=np.float64)
+        total += arr.nbytes
+        assert total <= 64 << 20, f"--dump-outputs: more than 64 MB at {name}"
+        np.save(os.path.join(path, name + (f".rank{rank}" if rank else "") + ".npy"), arr)
+    log(f"[bench] wrote {len(arrays)} arrays ({total / 1e6:.1f} MB) to {path}")
 
 
 def spawn_ranks(args):
@@ -377,7 +434,11 @@ def bench_solve(args, ba, sc, a0, b0, world, rank, barrier, torch, dist):
                    "parallelism": f"point-shard x{world}"},
         "lm": {"passes_per_solve": st.iterations, "accepted": st.accepted,
                "error_first": float(err[0]), "error_final": float(err[-1])},
+        "full": args.full,
     }
+    if args.dump_outputs:   # the last solve's error_ and parameters
+        a_out, b_out = ba.get_params()
+        dump_outputs(args.dump_outputs, rank, world, error=err, a=a_out, b=b_out)
     if rank == 0:
         print(json.dumps(out), flush=True)
     ba.close()
@@ -394,7 +455,8 @@ def bench_incremental(args):
     present (1 -> 8 elastic point sharding: rank threads, RCCL between
     distinct GPUs).  A step is one whole replay; value = BA solves/s."""
     print(json.dumps(replay_line(args.config, args.steps, args.warmup,
-                                 not args.no_cpu_baseline)), flush=True)
+                                 args.full and not args.no_cpu_baseline, args.full,
+                                 args.dump_outputs)), flush=True)
 
 
 def replay_summary(line):
@@ -413,9 +475,11 @@ def replay_summary(line):
     return out
 
 
-def replay_line(config, steps, warmup, with_cpu):
+def replay_line(config, steps, warmup, with_cpu, full, dump=None):
     """One growing-replay bench line (dict): `steps` timed replays after
-    `warmup` untimed ones."""
+    `warmup` untimed ones.  with_cpu: re-solve a sample of the last replay's
+    calls on the host; full: one more replay with every kernel timed (the
+    line's roofline); dump: the last timed replay's K, T, w, X to that folder."""
     import torch
     from bundleadjustmentmatlab_amd.dist import OBS_PER_SHARD
     from bundleadjustmentmatlab_amd.incremental import incremental_bundle
@@ -446,7 +510,7 @@ def replay_line(config, steps, warmup, with_cpu):
     def spy(K, T, w, X, pt, cam, ox, *opts, **kw):
         t1 = time.perf_counter()
         out = orig(K, T, w, X, pt, cam, ox, *opts, **kw)
-        if spy_on[0] and spy.count % k_every == 0:
+        if with_cpu and spy_on[0] and spy.count % k_every == 0:
             sample.append(dict(K=K, T=T, w=w, X=X, pt=pt, cam=cam, ox=ox, opts=opts,
                                gpu_s=time.perf_counter() - t1, passes=out[-1].iterations))
         spy.count += 1
@@ -520,9 +584,13 @@ def replay_line(config, steps, warmup, with_cpu):
         # rebuilt after a wrong prediction, built on the replay thread, and the
         # replay thread's wait for them by solve kind
         "prefetch": res.get("prefetch"),
-        "cpu_baseline": replay_cpu_baseline(sample, k_every, ncalls) if with_cpu else None,
+        "full": full,
     }
-    out["roofline"] = replay_roofline(sc, devices, dt / steps)
+    if dump:
+        dump_outputs(dump, K=res["K"], T=res["T"], w=res["w"], X=res["X"])
+    if full:
+        out["cpu_baseline"] = replay_cpu_baseline(sample, k_every, ncalls) if with_cpu else None
+        out["roofline"] = replay_roofline(sc, devices, dt / steps)
     return out
 
 

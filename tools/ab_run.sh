@@ -3,7 +3,7 @@
 # alternated R times; cfg3 pass unless BENCH_ARGS says otherwise.
 R=${R:-2}
 VARIANTS=${VARIANTS:-$(ls tools/build/ab)}
-ARGS=${BENCH_ARGS:---steps 20 --warmup 3 --no-cpu-baseline}
+ARGS=${BENCH_ARGS:---full --steps 20 --warmup 3 --no-cpu-baseline}
 mkdir -p gpurun_out
 : > gpurun_out/ab.log
 for r in $(seq $R); do

@@ -4,7 +4,7 @@ set -o pipefail
 out=${1:-gpurun_out/bench}
 mkdir -p "$out"
 step() { local name=$1 secs=$2; shift 2
-  timeout -k 10 "$secs" python3 -u bench.py "$@" > "$out/$name.log" 2>&1
+  timeout -k 10 "$secs" python3 -u bench.py --full "$@" > "$out/$name.log" 2>&1
   local rc=$?; echo "== $name rc=$rc"; grep '^{' "$out/$name.log" > "$out/$name.json"; return $rc; }
 step cfg3_pass 300 --steps 20 --warmup 3 &&
 step cfg3_solve 300 --mode solve --steps 5 --warmup 1 --no-cpu-baseline &&

@@ -4,12 +4,14 @@
 #   ab     bit identity of the working tree's library against tools/build/ab/base
 #          (tools/ab_build.sh base REV) on the long-track scenes (da_dump / da_compare)
 #   tests  pytest -m gpu (the whole GPU suite) -> gpurun_out/gputest.log
-#   cfg5x  bench.py --config cfg5x -> gpurun_out/bench_cfg5x.json
-#   cfg3   bench.py (default) -> gpurun_out/bench_cfg3.json
+#   cfg5x  bench.py --full --config cfg5x -> $BENCH_OUT/bench_cfg5x.json
+#   cfg3   bench.py --full (default config) -> $BENCH_OUT/bench_cfg3.json
+#          (BENCH_OUT: the folder of the bench lines, default bench_out)
 # usage: tools/gpu_batch.sh step [step ...]
 set -o pipefail
 export TMPDIR=/tmp
 mkdir -p gpurun_out
+out=${BENCH_OUT:-bench_out}
 for step in "$@"; do
   echo "== $step $(date +%T)"
   case $step in
@@ -28,13 +30,15 @@ for step in "$@"; do
         --timeout-method thread > gpurun_out/gputest.log 2>&1; rc=$?
       tail -5 gpurun_out/gputest.log; [ $rc -eq 0 ] || exit $rc ;;
     cfg5x)
-      timeout -k 10 600 python -u bench.py --config cfg5x > gpurun_out/bench_cfg5x.json \
-        2> gpurun_out/bench_cfg5x.log || exit 1
-      cat gpurun_out/bench_cfg5x.json ;;
+      mkdir -p "$out"
+      timeout -k 10 600 python -u bench.py --full --config cfg5x > "$out/bench_cfg5x.json" \
+        2> "$out/bench_cfg5x.log" || exit 1
+      cat "$out/bench_cfg5x.json" ;;
     cfg3)
-      timeout -k 10 600 python -u bench.py > gpurun_out/bench_cfg3.json \
-        2> gpurun_out/bench_cfg3.log || exit 1
-      cat gpurun_out/bench_cfg3.json ;;
+      mkdir -p "$out"
+      timeout -k 10 600 python -u bench.py --full > "$out/bench_cfg3.json" \
+        2> "$out/bench_cfg3.log" || exit 1
+      cat "$out/bench_cfg3.json" ;;
     *) echo "unknown step $step"; exit 2 ;;
   esac
 done
