@@ -12,7 +12,11 @@ model), fix_pivot (the pivot cameras' diagonals are exactly zero: the rule),
 fix_motion (every camera's), nomex semantics; and a banded scene whose
 five-camera groups are not fully co-visible, where the direct mode must stay
 off (the CR writes whole diagonal tiles back, so every lower entry of them
-has to be rewritten each pass).
+has to be rewritten each pass).  m = 30 is a whole number of five-camera
+tiles; m = 32 and 33 leave a partial (padded) last tile.  A pass that reports
+a non-positive pivot (the injected status of force_status) takes the pinv
+fallback, which forms S and e_ again: the direct mode's e_ then carries the
+zero-diagonal rule, k_assemble_tiles' does not -- the steps must still agree.
 """
 import os
 
@@ -61,15 +65,17 @@ def _assemble_launches(ba):
     return k.get("k_assemble", (0.0, 0))[1]
 
 
-@pytest.mark.parametrize("kind,kw", CASES)
-def test_direct_assembly_bit_identical(gpu, kind, kw):
-    sc = _banded()
+ROWS = 30      # camera-aligned CR tile: the 5 whole cameras of num_a = 6 that fit 32 rows
+
+
+def _bit_identical(gpu, kind, kw, m):
+    sc = _banded(m=m)
     a, b = _start(sc)
     res = {}
     for direct in (True, False):
         ba = _make(gpu, sc, kw, direct)
         plan = ba.plan_info()
-        assert plan["cr_levels"] > 0 and plan["cr_rows"] == 30, plan   # camera-aligned CR
+        assert plan["cr_levels"] > 0 and plan["cr_rows"] == ROWS, plan   # camera-aligned CR
         ba.set_params(a, b)
         steps = []
         for _ in range(4):
@@ -90,6 +96,52 @@ def test_direct_assembly_bit_identical(gpu, kind, kw):
     assert np.array_equal(e1, e0), (e1, e0)
     assert all(np.array_equal(x, y) for x, y in zip(p1, p0))
     assert pv1 == pv0
+
+
+@pytest.mark.parametrize("kind,kw", CASES)
+def test_direct_assembly_bit_identical(gpu, kind, kw):
+    _bit_identical(gpu, kind, kw, 30)
+
+
+@pytest.mark.parametrize("m", [32, 33])
+@pytest.mark.parametrize("kind,kw", CASES)
+def test_direct_assembly_bit_identical_partial_tile(gpu, kind, kw, m):
+    """The last tile holds 2 (m = 32) or 3 (m = 33) of its five cameras."""
+    _bit_identical(gpu, kind, kw, m)
+
+
+@pytest.mark.parametrize("kind,kw", CASES[:2])
+def test_direct_assembly_pinv_pass(gpu, kind, kw):
+    """force_status(4, 1): the next pass reports a non-positive pivot and takes
+    da = pinv(S) e_ (bundle_euclid.m:193) from a second Schur phase.  Single
+    step and whole run, direct mode against k_assemble_tiles, bit for bit --
+    plain, and with the pivot cameras' exactly-zero diagonals."""
+    sc = _banded(m=33)
+    a, b = _start(sc)
+    res = {}
+    for direct in (True, False):
+        ba = _make(gpu, sc, kw, direct)
+        ba.set_params(a, b)
+        ba.force_status(4, 1)
+        i = ba.step(relinearize=False, update_lm=True)
+        da, db = ba.last_step()
+        step = (i.old_sse, i.new_sse, i.dpg, i.accepted, i.lambda_, i.pinv, i.chol_failed)
+        j = ba.step(relinearize=False, update_lm=True)       # the hook is spent
+        ba.set_params(a, b)
+        ba.force_status(4, 1)
+        err, st = ba.run()
+        res[direct] = (step, da.copy(), db.copy(), j.pinv, err, st.pinv_passes, ba.get_params())
+        ba.close()
+    r1, r0 = res[True], res[False]
+    assert r1[0][5] == 1 and r1[3] == 0 and r1[5] == 1, (r1[0], r1[3], r1[5])
+    assert np.all(np.isfinite(r1[1])) and np.all(np.isfinite(r1[2]))
+    if kind == "pivot":
+        assert np.all(r1[1][:, :2] == 0.0)
+    assert r1[0] == r0[0], (kind, r1[0], r0[0])
+    assert np.array_equal(r1[1], r0[1]) and np.array_equal(r1[2], r0[2]), kind
+    assert r1[3] == r0[3] and r1[5] == r0[5]
+    assert np.array_equal(r1[4], r0[4]), (r1[4], r0[4])
+    assert all(np.array_equal(x, y) for x, y in zip(r1[6], r0[6]))
 
 
 def test_direct_assembly_off_without_full_groups(gpu):

@@ -1,0 +1,194 @@
+"""The extended-precision stage reference (tests/schur_ref.py) checked on the
+CPU before it judges a kernel (tests/test_gpu_stage_ref.py):
+
+* the oracle's own fp64 stages (sp_y / sp_schur / sp_update, a different
+  summation order from any GPU kernel) stay inside every per-entry bound;
+* the bounds have teeth: each of a list of small, realistic mistakes in S, in
+  the damping or in db leaves them;
+* the componentwise backward error separates a right solve (LAPACK Cholesky,
+  the oracle's fixed-row Cholesky: well below ld * u) from a solve of a system
+  with one 6 x 6 block missing (above 1e3 * ld * u).
+"""
+import functools
+
+import numpy as np
+import pytest
+
+import schur_ref as sr
+
+LAM = 1e-3
+SCENES = {
+    "cfg2-6": ("cfg2", dict(m=13, n=400, seed=3), 6),
+    "cfg2-7": ("cfg2", dict(m=13, n=400, seed=3), 7),
+    "cfg2-10": ("cfg2", dict(m=13, n=400, seed=3), 10),
+    "ladybug": ("ladybug", dict(m=40, n=1500, max_track=30, radius=150.0, seed=23), 6),
+    "cfg3-t10": ("cfg3", dict(m=40, n=2000, track=10, seed=6), 6),
+}
+
+
+def start_params(sc, num_a):
+    a = np.zeros((num_a, sc.m), order="F")
+    a[0:3], a[3:6] = sc.w0, sc.T0
+    if num_a == 7:
+        a[6] = sc.K[0]
+    elif num_a == 10:
+        a[6:10] = sc.K
+    return a, np.asfortranarray(sc.X0[:3])
+
+
+def w_of(W, na):
+    """The oracle's (N, 3 na) W as the getter's (na, 3, N)."""
+    return np.asfortranarray(W.T).reshape(na, 3, -1, order="F")
+
+
+@functools.lru_cache(maxsize=None)
+def _case(name, lam=LAM):
+    """One oracle pass of the scene at lam and the reference of its stages
+    (computed once, shared, never modified: the tests copy what they change)."""
+    import bundle_euclid_ref as oracle
+    from bundleadjustmentmatlab_amd.scene import make_config
+    cfg, kw, na = SCENES[name]
+    sc = make_config(cfg, **kw)
+    a, b = start_params(sc, na)
+    pb = oracle.SparseProblem(sc.m, sc.n, sc.obs_pt, sc.obs_cam, sc.obs_x, sc.K)
+    L = oracle.sp_linearize(pb, a, b, na)
+    Vi = oracle.pinv3_formula(sr.damp(L["V"], lam))
+    Y = oracle.sp_y(pb, L["W"], Vi, na)
+    S, e_ = oracle.sp_schur(pb, Y, L["W"], sr.damp(L["U"], lam), L["eA"], L["eB"], na)
+    ref = sr.schur(sc.m, sc.n, na, sc.obs_pt, sc.obs_cam, w_of(L["W"], na), L["V"], L["eB"],
+                   L["U"], L["eA"], lam)
+    return dict(sc=sc, na=na, a=a, b=b, pb=pb, L=L, Vi=Vi, Y=Y, S=S, e=e_.reshape(-1), ref=ref)
+
+
+def _ratios(c, S, e=None):
+    jk = c["ref"]["jk"]
+    return sr.schur_ratio(c["ref"], jk, sr.blocks_of(S, jk, c["na"]), c["e"] if e is None else e)
+
+
+@pytest.mark.parametrize("name", list(SCENES))
+def test_oracle_within_bounds(oracle, name):
+    c = _case(name)
+    na, sc = c["na"], c["sc"]
+    rs, re = _ratios(c, c["S"])
+    # every block of the oracle's S outside the reference's list is zero
+    full = np.zeros_like(c["S"])
+    for (j, k), B in zip(c["ref"]["jk"], sr.blocks_of(c["S"], c["ref"]["jk"], na)):
+        full[na * j:na * j + na, na * k:na * k + na] = B
+    assert np.array_equal(np.tril(full), np.tril(c["S"]))
+    da = oracle.chol_solve_fixed(c["S"], c["e"])
+    out = {}
+    for ndb in sorted({6, na}):
+        db = oracle.sp_update(c["pb"], c["L"]["W"], da, c["L"]["eB"], c["Vi"], c["a"], c["b"],
+                              na, ndb=ndb)[0]
+        rdb, bnd = sr.back_subst(na, ndb, sc.obs_pt, sc.obs_cam, w_of(c["L"]["W"], na), c["Vi"],
+                                 c["L"]["eB"], da)
+        out[ndb] = sr.db_ratio(db, rdb, bnd)
+    print(f"{name}: S {rs:.3g} e_ {re:.3g} db {out} of the bound")
+    assert rs <= 1.0 and re <= 1.0 and max(out.values()) <= 1.0
+
+
+def _offdiag_block(c, smallest=False):
+    """An off-diagonal block (index into ref): the one with the most points,
+    or the one of the smallest magnitude."""
+    r = c["ref"]
+    off = np.flatnonzero(r["jk"][:, 0] != r["jk"][:, 1])
+    if smallest:
+        mag = np.abs(r["S"][off]).max(axis=(1, 2)).astype(float)
+        return off[np.argmin(np.where(mag > 0, mag, np.inf))]
+    return off[np.argmax(r["npts"][off])]
+
+
+@pytest.mark.parametrize("name", ["cfg2-6", "cfg2-10", "ladybug"])
+def test_bound_has_teeth_on_s(oracle, name):
+    c = _case(name)
+    na, sc, r = c["na"], c["sc"], c["ref"]
+    sl = lambda j, k: (slice(na * j, na * j + na), slice(na * k, na * k + na))   # noqa: E731
+    assert max(_ratios(c, c["S"])) <= 1.0
+    # one point's term dropped from one off-diagonal block
+    j, k = r["jk"][_offdiag_block(c)]
+    pt, cam = sc.obs_pt, sc.obs_cam
+    i = np.intersect1d(pt[cam == j], pt[cam == k])[0]
+    oj = np.flatnonzero((pt == i) & (cam == j))[0]
+    ok = np.flatnonzero((pt == i) & (cam == k))[0]
+    term = c["Y"][oj].reshape(3, na).T @ c["L"]["W"][ok].reshape(3, na)
+    S = c["S"].copy()
+    S[sl(j, k)] += term
+    assert _ratios(c, S)[0] > 1.0
+    # one off-diagonal block transposed
+    S = c["S"].copy()
+    S[sl(j, k)] = S[sl(j, k)].T.copy()
+    assert _ratios(c, S)[0] > 1.0
+    # two cameras' diagonal blocks swapped
+    S = c["S"].copy()
+    S[sl(1, 1)], S[sl(2, 2)] = c["S"][sl(2, 2)], c["S"][sl(1, 1)]
+    assert _ratios(c, S)[0] > 1.0
+    # one entry of the smallest block off by 1e-10 relative
+    j, k = r["jk"][_offdiag_block(c, smallest=True)]
+    S = c["S"].copy()
+    B = S[sl(j, k)]
+    q = np.unravel_index(np.argmax(np.abs(B)), B.shape)
+    B[q] *= 1 + 1e-10
+    assert _ratios(c, S)[0] > 1.0
+    # one entry of e_ off by 1e-10 relative
+    e = c["e"].copy()
+    e[np.argmax(np.abs(e))] *= 1 + 1e-10
+    assert _ratios(c, c["S"], e)[1] > 1.0
+    # damped with 1.1e-3 where the reference has 1e-3
+    w = _case(name, 1.1e-3)
+    rs, re = _ratios(c, w["S"], w["e"])
+    assert rs > 1.0 and re > 1.0
+
+
+def test_bound_has_teeth_on_db(oracle):
+    """num_a = 10: the MEX back substitution takes six terms per observation
+    (mex_bundle_3_db_new.c:113-120); all ten is the nomex twin's."""
+    c = _case("cfg2-10")
+    na, sc = c["na"], c["sc"]
+    da = oracle.chol_solve_fixed(c["S"], c["e"])
+    assert np.abs(da.reshape(na, -1, order="F")[6:]).max() > 0
+    W = w_of(c["L"]["W"], na)
+    db = {ndb: oracle.sp_update(c["pb"], c["L"]["W"], da, c["L"]["eB"], c["Vi"], c["a"], c["b"],
+                                na, ndb=ndb)[0] for ndb in (6, na)}
+    for right, wrong in ((6, na), (na, 6)):
+        ref, bnd = sr.back_subst(na, right, sc.obs_pt, sc.obs_cam, W, c["Vi"], c["L"]["eB"], da)
+        assert sr.db_ratio(db[right], ref, bnd) <= 1.0
+        assert sr.db_ratio(db[wrong], ref, bnd) > 1.0
+    # one point's db off by 1e-10 relative
+    ref, bnd = sr.back_subst(na, 6, sc.obs_pt, sc.obs_cam, W, c["Vi"], c["L"]["eB"], da)
+    bad = db[6].copy()
+    bad[np.unravel_index(np.argmax(np.abs(bad)), bad.shape)] *= 1 + 1e-10
+    assert sr.db_ratio(bad, ref, bnd) > 1.0
+
+
+@pytest.mark.parametrize("name", ["cfg2-6", "cfg2-10", "ladybug", "cfg3-t10"])
+def test_residual_separates_right_from_wrong(oracle, name):
+    import scipy.linalg as sl
+    c = _case(name)
+    na = c["na"]
+    S, e = c["S"], c["e"]
+    ld = S.shape[0]
+    bar = ld * sr.U53
+    Ssym = sr.symmetrise(S)
+    x_lapack = sl.cho_solve(sl.cho_factor(Ssym, lower=True), e)
+    x_fixed = oracle.chol_solve_fixed(S, e)
+    eta = [sr.residual(np.tril(S), e, x) for x in (x_lapack, x_fixed)]
+    print(f"{name}: ld {ld} cond {np.linalg.cond(Ssym):.2g} eta / (ld u) "
+          f"{eta[0] / bar:.3g} {eta[1] / bar:.3g}")
+    assert max(eta) <= bar
+    # the same solves of a system with one 6 x 6 block (and its mirror) zeroed
+    j, k = c["ref"]["jk"][_offdiag_block(c)]
+    Sb = Ssym.copy()
+    Sb[na * j:na * j + 6, na * k:na * k + 6] = 0.0
+    Sb[na * k:na * k + 6, na * j:na * j + 6] = 0.0
+    xb = np.linalg.solve(Sb, e)      # (no longer positive definite in general)
+    assert sr.residual(np.tril(S), e, xb) > 1e3 * bar
+
+
+def test_residual_rows_and_exact_zeros():
+    """Fixed rows (zero row of S, zero e_, zero da) count as satisfied; a
+    non-zero residual over a zero denominator does not."""
+    S = np.diag([2.0, 0.0, 4.0])
+    assert sr.residual(S, [2.0, 0.0, 4.0], [1.0, 0.0, 1.0]) == 0.0
+    assert sr.residual(S, [2.0, 0.0, 4.0], [1.0, 0.0, 2.0]) > 0.1
+    assert sr.residual(S, [2.0, 0.0, 4.0], [1.0, 0.0, 2.0], rows=np.array([1, 1, 0], bool)) == 0.0
+    assert sr.residual(np.zeros((1, 1)), [0.0], [0.0]) == 0.0
