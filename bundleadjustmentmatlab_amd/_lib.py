@@ -14,7 +14,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # variant, tools/ab_build.sh); the package's own build otherwise
 LIB_PATH = os.environ.get("VLGBA_LIB") or os.path.join(_HERE, "libvlgba.so")
 
-ABI_VERSION = 5   # VLGBA_ABI_VERSION: the struct layouts below
+ABI_VERSION = 6   # VLGBA_ABI_VERSION: the struct layouts below
 
 c_int, c_double, c_ll = ctypes.c_int, ctypes.c_double, ctypes.c_longlong
 c_dp = ctypes.POINTER(ctypes.c_double)
@@ -96,6 +96,7 @@ SIGNATURES = {
     "vlgba_get_step": (c_int, [ctypes.c_void_p, c_dp, c_dp]),
     "vlgba_get_reduced_system": (c_int, [ctypes.c_void_p, c_ip, c_dp, c_dp]),
     "vlgba_get_linearization": (c_int, [ctypes.c_void_p, c_dp, c_dp, c_dp, c_dp, c_dp]),
+    "vlgba_covariance": (c_int, [ctypes.c_void_p, c_int, c_dp, c_dp, c_dp, c_dp]),
     "vlgba_sync": (c_int, [ctypes.c_void_p]),
     "vlgba_destroy": (None, [ctypes.c_void_p]),
     "vlgba_set_timing": (c_int, [ctypes.c_void_p, c_int]),
@@ -129,7 +130,8 @@ ERRORS = {-1001: "bad argument",
           -1002: "num_a must be 6, 7 or 10 (Euclidean) or 12 (projective)",
           -1003: "duplicate (point, camera) observation", -1004: "out of host memory",
           -1005: "RCCL communicator failure",
-          -1006: "library / header ABI mismatch"}
+          -1006: "library / header ABI mismatch",
+          -1007: "the undamped reduced camera system is not positive definite (gauge not fixed)"}
 
 _lib = None
 

@@ -366,6 +366,29 @@ class BundleAdjuster:
                 S[na * j:na * j + na, na * k:na * k + na] = B
         return S, e_
 
+    def covariance(self, scale=True, full=False):
+        """Posterior covariance at the current parameters (vlgba_covariance:
+        undamped, conditional on the fixed parameters, single rank): dict of
+        cam (na, na, m) the diagonal blocks of the camera covariance, pts
+        (3, 3, n) the point covariances, full (na m, na m) if ``full``, and
+        sse, dof, sigma2 = sse / dof, fixed_rows, ms (dense inverse, point
+        kernel) and scratch_bytes.  ``scale`` multiplies the matrices by
+        sigma2.  Raises VlgbaError (-1007) when the gauge is not fixed."""
+        na, ld = self.num_a, self.num_a * self.m
+        cam = np.zeros((na, na, self.m), order="F")
+        pts = np.zeros((3, 3, self.n), order="F")
+        S = np.zeros((ld, ld), order="F") if full else None
+        info = np.zeros(8)
+        check(self._L.vlgba_covariance(self._h, int(bool(scale)), _dp(cam),
+                                       _dp(S) if full else None, _dp(pts), _dp(info)),
+              "vlgba_covariance")
+        out = dict(cam=cam, pts=pts, sse=float(info[0]), dof=float(info[1]),
+                   sigma2=float(info[2]), fixed_rows=int(info[3]),
+                   ms=(float(info[4]), float(info[5])), scratch_bytes=int(info[6]))
+        if full:
+            out["full"] = S
+        return out
+
     def sync(self):
         check(self._L.vlgba_sync(self._h), "vlgba_sync")
 
@@ -469,12 +492,14 @@ def _adjuster_fingerprint(K, m, n, obs_pt, obs_cam, obs_x, o, num_vis, semantics
 
 def bundle_euclid_obs(K, Te, w, Xe, obs_pt, obs_cam, obs_x, *varargin, num_vis=0.0, device=0,
                       rank=0, world_size=1, comm_id=None, return_stats=False,
-                      semantics="mex", adjuster=None, **solver):
+                      semantics="mex", adjuster=None, return_covariance=False, **solver):
     """bundle_euclid on a COO observation list (0-based point / camera ids).
     ``solver`` keywords go to BundleAdjuster (parity, stop_rel, max_iter,
     max_iter2, lambda0, solver, ordered, schur_kernel).  ``adjuster``: a handle
     made beforehand by euclid_obs_adjuster for the same problem and options
-    (or a concurrent.futures.Future of one); it is used and closed here."""
+    (or a concurrent.futures.Future of one); it is used and closed here.
+    ``return_covariance`` appends BundleAdjuster.covariance() at the returned
+    parameters (after the stats, when both are asked for)."""
     K, Te, w, Xe = _F(K), _F(Te), _F(w), _F(Xe)
     m, n = w.shape[1], Xe.shape[1]
     nomex = semantics == "nomex"
@@ -501,13 +526,17 @@ def bundle_euclid_obs(K, Te, w, Xe, obs_pt, obs_cam, obs_x, *varargin, num_vis=0
         ba.set_params(a, b)
         err, st = ba.run()
         a, b = ba.get_params()
+        if return_covariance:
+            ba.set_params(a, b)   # a linearisation of its own at the returned point
+            cov = ba.covariance()
     # Xe_(4,:): the input's (bundle_euclid.m:267) or ones (bundle_euclid_nomex.m:364)
     out = unpack(K, a, b, np.ones((1, n)) if nomex else Xe[3:4], nvk) + (err,)
-    return out + (st,) if return_stats else out
+    out = out + (st,) if return_stats else out
+    return out + (cov,) if return_covariance else out
 
 
 def bundle_euclid(K, Te, w, Xe, x, *varargin, device=0, return_stats=False, semantics="mex",
-                  **solver):
+                  return_covariance=False, **solver):
     """[K_ Te_ w_ Xe_ error_] = bundle_euclid(K, Te, w, Xe, x, ...)  (bundle_euclid.m:1)."""
     x = _F(x)
     m, n = np.shape(w)[1], x.shape[1]
@@ -531,15 +560,17 @@ def bundle_euclid(K, Te, w, Xe, x, *varargin, device=0, return_stats=False, sema
         k += 1
     return bundle_euclid_obs(K, Te, w, Xe, pt, cam, obs_x, *rest, num_vis=num_vis,
                              device=device, return_stats=return_stats, semantics=semantics,
-                             **solver)
+                             return_covariance=return_covariance, **solver)
 
 
-def bundle_euclid_nomex(K, Te, w, Xe, x, *varargin, device=0, return_stats=False, **solver):
+def bundle_euclid_nomex(K, Te, w, Xe, x, *varargin, device=0, return_stats=False,
+                        return_covariance=False, **solver):
     """[K_ Te_ w_ Xe_ error_] = bundle_euclid_nomex(K, Te, w, Xe, x, ...)
     (bundle_euclid_nomex.m:1): the same LM loop with the twin's semantics --
     db from every camera parameter (:268-277), no 'fix_pivot', Xe_(4,:) = 1."""
     return bundle_euclid(K, Te, w, Xe, x, *varargin, device=device,
-                         return_stats=return_stats, semantics="nomex", **solver)
+                         return_stats=return_stats, semantics="nomex",
+                         return_covariance=return_covariance, **solver)
 
 
 def bundle_euclid_resect(K, Te, w, Xs, xs, *varargin, device=0, max_iter=0, max_iter2=0,

@@ -374,6 +374,38 @@ int ba_chol_solve(ba_dev *d, int nospin = 0);
 int ba_pinv_apply(ba_dev *d, const double *V, const double *ev, long long ld, const double *rhs,
                   double *work, double *da);
 
+// ---- ba_cov.hip (vlgba_covariance) ----
+// track-length bins of k_point_cov: up to BA_COV_T8 views 8 lanes per point,
+// up to BA_COV_T64 one wave, longer one workgroup; a long track's W rows are
+// staged in LDS while they fit BA_COV_LDS bytes
+#define BA_COV_T8 8
+#define BA_COV_T64 32
+#define BA_COV_LDS 65536
+// fixed[r] = 1 for the exactly-zero rows of the dense lower S (before
+// ba_fix_diag_plain gives them a unit diagonal)
+int ba_cov_mark_fixed(ba_dev *d, const double *S, long long ld, unsigned char *fixed);
+// the lower-triangle inverse -> full symmetric with the fixed rows / columns
+// zeroed, and its diagonal blocks (na x na x m)
+int ba_cov_finish(ba_dev *d, double *S, long long ld, const unsigned char *fixed, double *blocks);
+// where k_point_cov reads Sigma_a[j,k] (k <= j): the finished dense inverse
+// (packed == NULL), or a packed copy of its co-visible blocks -- block p of
+// camera row j at rowptr[j] <= p < rowptr[j + 1] has column camera col[p]
+// (ascending within a row), NA x NA doubles column major
+struct ba_cov_src {
+    const double *Sa;
+    long long ld;
+    const int *rowptr, *col;
+    const double *packed;
+};
+// packed[p] = block (bj[p], bk[p]) of the dense S, p < nb
+int ba_cov_pack(ba_dev *d, const double *S, long long ld, const int *bj, const int *bk, int nb,
+                double *packed);
+// Sigma_b of the points list[0 .. n8 + n64 + nwg) (internal order, binned by
+// track length as above; tmax: the longest track) into out [n][9]; reads d->W
+// and d->Vinv (lambda = 0)
+int ba_launch_point_cov(ba_dev *d, const int *list, int n8, int n64, int nwg, int tmax,
+                        const ba_cov_src *src, double *out);
+
 #define TRY_RC(x)                                                                   \
     do {                                                                            \
         int rc__ = (x);                                                             \

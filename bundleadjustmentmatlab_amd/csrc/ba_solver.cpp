@@ -1256,6 +1256,19 @@ struct vlgba_ctx {
     int spin_retries = 0;         // passes re-solved after a hand-off timeout
     int debug_timeouts = 0;       // test hooks: passes whose timeout word / pivot word
     int debug_pivots = 0;         // is forced (vlgba_debug_force_status)
+    // vlgba_covariance (allocated on its first call): the points binned by track
+    // length for k_point_cov (internal order: 8 lanes | one wave | one workgroup
+    // per point), the longest track, the points with an observation, the
+    // fixed-row mask of S0, the diagonal blocks of Sigma_a and Sigma_b
+    int *cov_list = nullptr;
+    int cov_n8 = 0, cov_n64 = 0, cov_nwg = 0, cov_tmax = 0, cov_seen = 0;
+    unsigned char *cov_fixed = nullptr;
+    double *cov_diag = nullptr, *cov_pts = nullptr;
+    // ... and the packed copy of Sigma_a's co-visible blocks k_point_cov reads
+    // (CSR by camera row: cov_rowptr [m + 1], cov_col / cov_bj [nb];
+    // VLGBA_COV_PACKED=0: none, the kernel reads the dense inverse -- A/B)
+    int *cov_rowptr = nullptr, *cov_col = nullptr, *cov_bj = nullptr;
+    double *cov_packed = nullptr;
 };
 
 // Per-device pool of the context's streams, fork/join events and host-mapped
@@ -2172,6 +2185,8 @@ struct rs_api {
     rocblas_status (*potrs)(rocblas_handle, const rocblas_fill, const rocblas_int,
                             const rocblas_int, double *, const rocblas_int, double *,
                             const rocblas_int);
+    rocblas_status (*potri)(rocblas_handle, const rocblas_fill, const rocblas_int, double *,
+                            const rocblas_int, rocblas_int *);
     bool ok = false;
 };
 rs_api *rs_load()
@@ -2187,6 +2202,7 @@ rs_api *rs_load()
         api.syevd = (decltype(api.syevd))dlsym(h, "rocsolver_dsyevd");
         api.potrf = (decltype(api.potrf))dlsym(h, "rocsolver_dpotrf");
         api.potrs = (decltype(api.potrs))dlsym(h, "rocsolver_dpotrs");
+        api.potri = (decltype(api.potri))dlsym(h, "rocsolver_dpotri");
         api.ok = api.create && api.set_stream && api.syevd;
     });
     return api.ok ? &api : nullptr;
@@ -2758,6 +2774,198 @@ int vlgba_get_reduced_system(vlgba_ctx *c, int *blk_jk, double *blocks, double *
     if (e_) TRY(download(e_, d.rhs, (size_t)d.ld, d.stream));
     VLGBA_CHECK(hipStreamSynchronize(d.stream));
     return 0;
+}
+
+// vlgba_covariance's per-context setup: the points binned by track length
+// (ba_cov.hip) and the device buffers of its results
+static int cov_setup(vlgba_ctx *c)
+{
+    ba_dev &d = c->d;
+    if (c->cov_pts) return 0;
+    std::vector<int> ptr((size_t)d.n + 1);
+    TRY(download(ptr.data(), d.pt_ptr, (size_t)d.n + 1, d.stream));
+    VLGBA_CHECK(hipStreamSynchronize(d.stream));
+    std::vector<int> bin[3];
+    int tmax = 0, seen = 0;
+    for (int i = 0; i < d.n; i++) {
+        const int t = ptr[i + 1] - ptr[i];
+        bin[t <= BA_COV_T8 ? 0 : t <= BA_COV_T64 ? 1 : 2].push_back(i);
+        tmax = std::max(tmax, t);
+        seen += t > 0;
+    }
+    std::vector<int> list;
+    list.reserve((size_t)d.n);
+    for (const auto &b : bin) list.insert(list.end(), b.begin(), b.end());
+    TRY(ctx_alloc(c, &c->cov_list, std::max<size_t>(1, list.size())));
+    TRY(upload(c->cov_list, list.data(), list.size(), d.stream));
+    VLGBA_CHECK(hipStreamSynchronize(d.stream));   // list goes out of scope
+    const char *pk = std::getenv("VLGBA_COV_PACKED");
+    if (!(pk && pk[0] == '0')) {
+        // the co-visible blocks (j >= k) by camera row j, columns ascending
+        std::vector<int> jk(2 * (size_t)d.nb);
+        TRY(download(jk.data(), d.blk_jk, jk.size(), d.stream));
+        VLGBA_CHECK(hipStreamSynchronize(d.stream));
+        std::vector<int> ord((size_t)d.nb);
+        std::iota(ord.begin(), ord.end(), 0);
+        std::sort(ord.begin(), ord.end(), [&](int x, int y) {
+            return jk[2 * (size_t)x] != jk[2 * (size_t)y] ? jk[2 * (size_t)x] < jk[2 * (size_t)y]
+                                                          : jk[2 * (size_t)x + 1] < jk[2 * (size_t)y + 1];
+        });
+        std::vector<int> rowptr((size_t)d.m + 1, 0), col((size_t)d.nb), bj((size_t)d.nb);
+        for (int p = 0; p < d.nb; p++) {
+            bj[p] = jk[2 * (size_t)ord[p]];
+            col[p] = jk[2 * (size_t)ord[p] + 1];
+            if (bj[p] < 0 || bj[p] >= d.m || col[p] < 0 || col[p] > bj[p]) return VLGBA_E_ARG;
+            rowptr[(size_t)bj[p] + 1]++;
+        }
+        for (int j = 0; j < d.m; j++) rowptr[(size_t)j + 1] += rowptr[j];
+        TRY(ctx_alloc(c, &c->cov_rowptr, rowptr.size()));
+        TRY(ctx_alloc(c, &c->cov_col, std::max<size_t>(1, col.size())));
+        TRY(ctx_alloc(c, &c->cov_bj, std::max<size_t>(1, bj.size())));
+        TRY(upload(c->cov_rowptr, rowptr.data(), rowptr.size(), d.stream));
+        TRY(upload(c->cov_col, col.data(), col.size(), d.stream));
+        TRY(upload(c->cov_bj, bj.data(), bj.size(), d.stream));
+        VLGBA_CHECK(hipStreamSynchronize(d.stream));
+        // one block more than nb: the bisection of an empty row ends there
+        TRY(ctx_alloc(c, &c->cov_packed, ((size_t)d.nb + 1) * d.na * d.na));
+        VLGBA_CHECK(hipMemsetAsync(c->cov_packed, 0,
+                                   sizeof(double) * ((size_t)d.nb + 1) * d.na * d.na, d.stream));
+    }
+    TRY(ctx_alloc(c, &c->cov_fixed, (size_t)std::max(1LL, d.ld)));
+    TRY(ctx_alloc(c, &c->cov_diag, std::max<size_t>(1, (size_t)d.na * d.na * d.m)));
+    c->cov_n8 = (int)bin[0].size();
+    c->cov_n64 = (int)bin[1].size();
+    c->cov_nwg = (int)bin[2].size();
+    c->cov_tmax = tmax;
+    c->cov_seen = seen;
+    TRY(ctx_alloc(c, &c->cov_pts, std::max<size_t>(1, 9 * (size_t)d.n)));
+    return 0;
+}
+
+static int cov_run(vlgba_ctx *c, int scale, double *cov_a, double *cov_a_full, double *cov_b,
+                   double *info)
+{
+    ba_dev &d = c->d;
+    rs_api *rs = nullptr;
+    rocblas_handle hdl = nullptr;
+    TRY(rs_prepare(c, &rs, &hdl));
+    if (!rs->potrf || !rs->potri) return VLGBA_E_ARG;
+    TRY(cov_setup(c));
+    const long long ld = d.ld;
+    // stage 1 at the current parameters, as a pass would run it
+    if (!c->lin_valid || c->camred_due) {
+        if (!c->lin_valid) TRY(ba_launch_linearize(&d, c->flags));
+        TRY(ba_launch_camera_reduce(&d, c->flags));
+        if (d.parity) TRY(ba_launch_parity_old_sse(&d));
+        if (d.ordered)
+            VLGBA_CHECK(hipMemcpyAsync(d.eA + d.ld, d.scal + 0, sizeof(double),
+                                       hipMemcpyDeviceToDevice, d.stream));
+        c->lin_valid = 1;
+        c->camred_due = 0;
+    }
+    hipEvent_t ev[3] = {};
+    for (auto &e : ev) VLGBA_CHECK(hipEventCreate(&e));
+    auto run = [&]() -> int {
+        VLGBA_CHECK(hipEventRecord(ev[0], d.stream));
+        // S0: the undamped Schur phase (it also leaves V+ = vlg_pinv3(V) in d.Vinv),
+        // dense lower triangle, unit diagonal on the exactly-zero rows
+        TRY(schur_phase(c, 0.0));
+        if (d.join_pending) {
+            VLGBA_CHECK(hipStreamWaitEvent(d.stream, d.ev_join, 0));
+            d.join_pending = 0;
+        }
+        TRY(ba_launch_assemble_plain(&d, c->pinv_S, ld, 1));
+        TRY(ba_cov_mark_fixed(&d, c->pinv_S, ld, c->cov_fixed));
+        TRY(ba_fix_diag_plain(&d, c->pinv_S, ld));
+        // the library stream is non-blocking: S0 complete before rocSOLVER
+        VLGBA_CHECK(hipStreamSynchronize(d.stream));
+        {
+            std::lock_guard<std::mutex> lk(g_rs_mu);
+            int pinfo = 0;
+            if (rs->set_stream(hdl, d.stream) != rocblas_status_success ||
+                rs->potrf(hdl, rocblas_fill_lower, (rocblas_int)ld, c->pinv_S, (rocblas_int)ld,
+                          c->pinv_info) != rocblas_status_success)
+                return VLGBA_E_ARG;
+            VLGBA_CHECK(hipMemcpyAsync(&pinfo, c->pinv_info, sizeof pinfo, hipMemcpyDeviceToHost,
+                                       d.stream));
+            VLGBA_CHECK(hipStreamSynchronize(d.stream));
+            if (pinfo != 0) return VLGBA_E_SINGULAR;
+            if (rs->potri(hdl, rocblas_fill_lower, (rocblas_int)ld, c->pinv_S, (rocblas_int)ld,
+                          c->pinv_info) != rocblas_status_success)
+                return VLGBA_E_ARG;
+            VLGBA_CHECK(hipMemcpyAsync(&pinfo, c->pinv_info, sizeof pinfo, hipMemcpyDeviceToHost,
+                                       d.stream));
+            VLGBA_CHECK(hipStreamSynchronize(d.stream));
+            if (pinfo != 0) return VLGBA_E_SINGULAR;
+        }
+        TRY(ba_cov_finish(&d, c->pinv_S, ld, c->cov_fixed, c->cov_diag));
+        if (c->cov_packed)
+            TRY(ba_cov_pack(&d, c->pinv_S, ld, c->cov_bj, c->cov_col, d.nb, c->cov_packed));
+        VLGBA_CHECK(hipEventRecord(ev[1], d.stream));
+        const ba_cov_src src{c->pinv_S, ld, c->cov_rowptr, c->cov_col, c->cov_packed};
+        TRY(ba_launch_point_cov(&d, c->cov_list, c->cov_n8, c->cov_n64, c->cov_nwg, c->cov_tmax,
+                                &src, c->cov_pts));
+        VLGBA_CHECK(hipEventRecord(ev[2], d.stream));
+        VLGBA_CHECK(hipStreamSynchronize(d.stream));
+        return 0;
+    };
+    int rc = run();
+    float ms_a = 0.f, ms_b = 0.f;
+    if (!rc) {
+        (void)hipEventElapsedTime(&ms_a, ev[0], ev[1]);
+        (void)hipEventElapsedTime(&ms_b, ev[1], ev[2]);
+    } else {
+        (void)hipStreamSynchronize(d.stream);
+    }
+    for (auto &e : ev) (void)hipEventDestroy(e);
+    TRY(rc);
+    // SSE / dof: the linearisation's SSE (the old SSE of a pass from here)
+    double sse = 0.0;
+    std::vector<unsigned char> fixed((size_t)ld);
+    TRY(download(&sse, d.eA + d.ld, 1, d.stream));
+    TRY(download(fixed.data(), c->cov_fixed, (size_t)ld, d.stream));
+    VLGBA_CHECK(hipStreamSynchronize(d.stream));
+    long long nfixed = 0;
+    for (unsigned char f : fixed) nfixed += f;
+    const double dof = 2.0 * (double)d.N -
+                       ((double)(ld - nfixed) + (c->flags.fix_structure ? 0.0 : 3.0 * c->cov_seen));
+    const double sigma2 = dof > 0 ? sse / dof : 0.0;
+    if (info) {
+        const double v[8] = {sse, dof, sigma2, (double)nfixed, ms_a, ms_b,
+                             8.0 * (double)ld * (double)ld, 0.0};
+        std::memcpy(info, v, sizeof v);
+    }
+    if (scale && !(dof > 0)) return VLGBA_E_ARG;
+    const size_t na2m = (size_t)d.na * d.na * d.m;
+    if (cov_a) TRY(download(cov_a, c->cov_diag, na2m, d.stream));
+    if (cov_a_full) TRY(download(cov_a_full, c->pinv_S, (size_t)(ld * ld), d.stream));
+    if (cov_b) TRY(download_points(c, cov_b, c->cov_pts, 9));
+    VLGBA_CHECK(hipStreamSynchronize(d.stream));
+    if (scale) {
+        for (size_t q = 0; cov_a && q < na2m; q++) cov_a[q] *= sigma2;
+        for (size_t q = 0; cov_a_full && q < (size_t)(ld * ld); q++) cov_a_full[q] *= sigma2;
+        for (size_t q = 0; cov_b && q < 9 * (size_t)d.n; q++) cov_b[q] *= sigma2;
+    }
+    return 0;
+}
+
+int vlgba_covariance(vlgba_ctx *c, int scale, double *cov_a, double *cov_a_full, double *cov_b,
+                     double *info)
+{
+    if (!c) return VLGBA_E_ARG;
+    // one rank only: the sharded form (an all-reduce of S0 and per-rank point
+    // blocks) is not built, and no collective runs here
+    if (c->world > 1 || c->comm || c->host_allreduce) return VLGBA_E_ARG;
+    TRY(ctx_enter(c));
+    // the call's launches stay out of the pass timers
+    const int timing = c->timing;
+    const int kt_on = c->d.kt ? c->d.kt->on : 0;
+    c->timing = 0;
+    if (c->d.kt) c->d.kt->on = 0;
+    const int rc = cov_run(c, scale, cov_a, cov_a_full, cov_b, info);
+    c->timing = timing;
+    if (c->d.kt) c->d.kt->on = kt_on;
+    return rc;
 }
 
 int vlgba_get_step(vlgba_ctx *c, double *da, double *db)

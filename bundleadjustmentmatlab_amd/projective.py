@@ -74,10 +74,12 @@ def unpack(a, b, Xp4):
 
 def bundle_projective_obs(Pp, Xp, obs_pt, obs_cam, obs_x, *varargin, num_vis=0.0, device=0,
                           rank=0, world_size=1, comm_id=None, return_stats=False,
-                          semantics="mex", **solver_kw):
+                          semantics="mex", return_covariance=False, **solver_kw):
     """bundle_projective on a COO observation list (0-based point / camera ids);
     varargin takes 'fix_structure', 'fix_motion', 'verbose' (visibility is the
-    list itself)."""
+    list itself).  ``return_covariance`` appends BundleAdjuster.covariance()
+    at the returned parameters (the projective model fixes no gauge: expect
+    VlgbaError -1007 or very large values unless the structure is fixed)."""
     Pp, Xp = _F(Pp), _F(Xp)
     m, n = Pp.shape[2], Xp.shape[1]
     o = parse_options(m, n, varargin, x=np.zeros((2, n, m)))
@@ -91,12 +93,16 @@ def bundle_projective_obs(Pp, Xp, obs_pt, obs_cam, obs_x, *varargin, num_vis=0.0
         ba.set_params(a, b)
         err, st = ba.run()
         a, b = ba.get_params()
+        if return_covariance:
+            ba.set_params(a, b)   # a linearisation of its own at the returned point
+            cov = ba.covariance()
     out = unpack(a, b, Xp[3:4]) + (err,)
-    return out + (st,) if return_stats else out
+    out = out + (st,) if return_stats else out
+    return out + (cov,) if return_covariance else out
 
 
 def bundle_projective(Pp, Xp, x, *varargin, device=0, return_stats=False, semantics="mex",
-                      **solver_kw):
+                      return_covariance=False, **solver_kw):
     """[Pp_ Xp_ error_] = bundle_projective(Pp, Xp, x, ...) (bundle_projective.m:1)."""
     x, Pp = _F(x), _F(Pp)
     m, n = Pp.shape[2], x.shape[1]
@@ -114,7 +120,8 @@ def bundle_projective(Pp, Xp, x, *varargin, device=0, return_stats=False, semant
         rest.append(varargin[k])
         k += 1
     return bundle_projective_obs(Pp, Xp, pt, cam, obs_x, *rest, num_vis=num_vis, device=device,
-                                 return_stats=return_stats, semantics=semantics, **solver_kw)
+                                 return_stats=return_stats, semantics=semantics,
+                                 return_covariance=return_covariance, **solver_kw)
 
 
 def bundle_projective_nomex(Pp, Xp, x, *varargin, device=0, return_stats=False, **solver_kw):

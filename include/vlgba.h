@@ -26,6 +26,8 @@ extern "C" {
 #define VLGBA_E_NOMEM (-1004)    /* host allocation failed                    */
 #define VLGBA_E_COMM (-1005)     /* RCCL failure                              */
 #define VLGBA_E_ABI (-1006)      /* caller built against another vlgba.h      */
+#define VLGBA_E_SINGULAR (-1007) /* vlgba_covariance: the undamped reduced camera
+                                    system is not positive definite (gauge)   */
 
 /* ABI of this header.  Bumped whenever a public struct, constant or entry
  * point changes: 1 = the round-1/2 layouts; 2 = vlgba_stats.pinv_passes /
@@ -33,11 +35,12 @@ extern "C" {
  * vlgba_stats.nd_retries, vlgba_step_info.nd_retry, vlgba_comm_release,
  * VLGBA_NKERNELS 18 (k_update_linearize), vlgba_kernel_flops; 4 =
  * vlgba_debug_dehom; 5 = vlgba_debug_dehom removed, VLGBA_NPLAN 29 (the
- * envelope runner's launch count), vlgba_debug_force_status word 6.  Callers
+ * envelope runner's launch count), vlgba_debug_force_status word 6; 6 =
+ * vlgba_covariance, VLGBA_E_SINGULAR.  Callers
  * check it once at load time with VLGBA_ABI_CHECK() (the MEX gateways and the Python
  * loader do): the library compares the version and the struct sizes the
  * caller was compiled with against its own and returns 0 or VLGBA_E_ABI. */
-#define VLGBA_ABI_VERSION 5
+#define VLGBA_ABI_VERSION 6
 
 /* camera models (vlgba_problem.model) */
 #define VLGBA_MODEL_EUCLIDEAN 0   /* bundle_euclid.m: a = [w; T; (K)], num_a 6/7/10     */
@@ -223,6 +226,46 @@ int vlgba_get_step(vlgba_ctx *ctx, double *da, double *db);
  * vlgba_plan_info [10]) with their camera pairs blk_jk [2 * count], and e_
  * (num_a * m).  Linearises first if the parameters changed.  NULL skips. */
 int vlgba_get_reduced_system(vlgba_ctx *ctx, int *blk_jk, double *blocks, double *e_);
+/* Posterior covariance at the context's parameters (linearises first if they
+ * changed, as vlgba_get_reduced_system does), undamped (lambda = 0), with the
+ * context's fix masks applied exactly as a pass applies them
+ * (bundle_euclid.m:140-154):
+ *   S0      = U - sum_i W_i V+_i W_i^T               reduced camera system
+ *   Sigma_a = S0^-1                                   (num_a m)^2
+ *   Sigma_b_i = V+_i + V+_i (sum_{j,k in cams(i)} W_ij^T Sigma_a[j,k] W_ik) V+_i
+ *   sigma2  = SSE / dof,  dof = 2 num_obs - (free camera rows
+ *             + 3 (points with an observation, or 0 under fix_structure))
+ * V+_i is the 3x3 pseudo-inverse the passes use at lambda = 0 (the same code).
+ *   cov_a       [num_a x num_a x m]  diagonal blocks of Sigma_a   (NULL: skip)
+ *   cov_a_full  [ld x ld], ld = num_a*m, full symmetric Sigma_a   (NULL: skip)
+ *   cov_b       [3 x 3 x n]          Sigma_b_i                    (NULL: skip)
+ *   info        [8] or NULL: [0] SSE  [1] dof  [2] sigma2  [3] fixed rows
+ *               [4] ms assemble + factor + inverse   [5] ms point kernel
+ *               [6] device bytes of dense scratch    [7] 0
+ * scale != 0 multiplies every output by sigma2 (VLGBA_E_ARG when dof <= 0;
+ * info is written first).
+ * Fixed parameters: a row of S0 that is exactly zero (a pivot camera, every
+ * camera under fix_motion, a camera without observations, the rotation rows
+ * of a camera with |w| < 1e-6) is factored with a unit diagonal, as the
+ * passes do, and its row and column are exactly 0 in every output.  An unseen
+ * point, and every point under fix_structure, has Sigma_b_i = 0 exactly.
+ * Gauge: the covariance is conditional on what the caller fixed.  When the
+ * Cholesky factorisation (rocSOLVER dpotrf, then dpotri) meets a non-positive
+ * pivot the call returns VLGBA_E_SINGULAR and writes no covariance; no
+ * pseudo-inverse (free-gauge) covariance is attempted.  The Jacobians are the
+ * reference's forward differences (h = 1e-10): an unfixed gauge usually leaves
+ * S0 ill-conditioned rather than exactly singular, the call then succeeds with
+ * the large values that implies, and every value carries the Jacobians'
+ * relative noise of about 1e-6.
+ * One rank only: VLGBA_E_ARG for world_size > 1 (with or without a
+ * communicator); VLGBA_E_ARG too when rocSOLVER or its dpotrf / dpotri are not
+ * available.  Uses 8 ld^2 bytes of device scratch (the pinv fallback's
+ * buffer; cfg3: 288 MB).  A selected inverse on the solver's own factors,
+ * which avoids the dense ld^2 step, is not built.
+ * The call leaves the LM state as it was: the next vlgba_step gives the same
+ * bits as without it, vlgba_get_step still returns the last pass's step. */
+int vlgba_covariance(vlgba_ctx *ctx, int scale, double *cov_a, double *cov_a_full,
+                     double *cov_b, double *info);
 int vlgba_sync(vlgba_ctx *ctx);
 void vlgba_destroy(vlgba_ctx *ctx);
 /* device-kernel timing of the last vlgba_step, milliseconds per phase:

@@ -8,6 +8,7 @@
 //   tools/bench_plan.cpp <the library's kernel objects> -lrccl -o tools/build/bench_plan
 // Input: int32 m, n, N, then int32 obs_pt[N], int32 obs_cam[N].
 #include "../bundleadjustmentmatlab_amd/csrc/ba_solver.cpp"
+#include "../bundleadjustmentmatlab_amd/csrc/ba_cov.hip"   // ba_solver.cpp's covariance launchers
 
 #include <chrono>
 #include <cstdio>
