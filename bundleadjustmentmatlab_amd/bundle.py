@@ -25,7 +25,7 @@ from __future__ import annotations
 import ctypes
 import numpy as np
 
-from ._lib import (ALLREDUCE_FN, MODEL_EUCLIDEAN, MODEL_PROJECTIVE, NKERNELS, ON_PASS_FN,
+from ._lib import (ALLREDUCE_FN, LOSSES, MODEL_EUCLIDEAN, MODEL_PROJECTIVE, NKERNELS, ON_PASS_FN,
                    VlgbaOptions,
                    VlgbaProblem, VlgbaResectProblem, VlgbaStats,
                    VlgbaStepInfo, c_dp, c_ip, c_up, check, lib)
@@ -208,6 +208,9 @@ class BundleAdjuster:
     SSE, error_ values (SSE / num_vis), rho, accepted, chol_failed, pinv.
     ``model="projective"`` solves bundle_projective.m instead: num_a = 12
     (a = P(:) per camera), K is None and ``m`` gives the camera count.
+    ``loss`` ("none", "huber" or "cauchy") with ``loss_scale`` in pixels makes
+    the solve robust (set_loss; vlgba_set_loss): error_ and the pass scalars
+    are then the robust cost.  Not with ``parity`` / ``ordered``.
     """
     SOLVERS = {"auto": 0, "dense": 1, "envelope": 2, "sequential": 3, "nd": 4}
     SCHUR_KERNELS = {"auto": 0, "terms": 1}
@@ -219,8 +222,13 @@ class BundleAdjuster:
                  rank=0, world_size=1, comm_id=None, max_iter=0, max_iter2=0, lambda0=0.0,
                  dense_solve=False, ordered=False, allreduce=None, solver=None,
                  schur_kernel="auto", semantics="mex", model="euclidean", m=None,
-                 parity=False, stop_rel=0.0, log=None):
+                 parity=False, stop_rel=0.0, log=None, loss="none", loss_scale=0.0):
         L = lib()
+        if loss not in LOSSES:
+            raise ValueError(f"loss must be one of {sorted(LOSSES)}")
+        if loss != "none" and (parity or ordered):
+            raise ValueError("a robust loss does not go with parity / ordered mode (bit parity "
+                             "with a reference that has no loss)")
         solve_mode = self.SOLVERS[solver] if solver is not None else int(bool(dense_solve))
         self.K = _F(K) if K is not None else None
         self.m = int(m) if m is not None else self.K.shape[1]
@@ -273,6 +281,39 @@ class BundleAdjuster:
               "vlgba_create")
         self._h = h
         self._L = L
+        if loss != "none":
+            try:
+                self.set_loss(loss, loss_scale)
+            except Exception:
+                self.close()
+                raise
+
+    def set_loss(self, loss="none", scale=0.0):
+        """The robust loss of the passes from here on (vlgba_set_loss): "none",
+        "huber" or "cauchy" with ``scale`` in pixels.  The next pass or getter
+        linearises again with the new weights."""
+        if loss not in LOSSES:
+            raise ValueError(f"loss must be one of {sorted(LOSSES)}")
+        check(self._L.vlgba_set_loss(self._h, LOSSES[loss], float(scale)), "vlgba_set_loss")
+
+    def get_loss(self):
+        """(loss name, scale) of the context (vlgba_get_loss)."""
+        kind, scale = ctypes.c_int(), ctypes.c_double()
+        check(self._L.vlgba_get_loss(self._h, ctypes.byref(kind), ctypes.byref(scale)),
+              "vlgba_get_loss")
+        return {v: k for k, v in LOSSES.items()}[kind.value], scale.value
+
+    def residuals(self):
+        """Per observation at the current parameters (vlgba_get_residuals), in
+        linearization()'s W order: e (N, 2) the unweighted residuals x - x_hat,
+        w (N,) the loss's weights and rho (N,) its costs (no loss: 1 and
+        e0^2 + e1^2)."""
+        e = np.zeros((self.num_obs, 2))
+        w = np.zeros(self.num_obs)
+        rho = np.zeros(self.num_obs)
+        check(self._L.vlgba_get_residuals(self._h, _dp(e), _dp(w), _dp(rho)),
+              "vlgba_get_residuals")
+        return e, w, rho
 
     def close(self):
         if getattr(self, "_h", None):
@@ -445,7 +486,8 @@ class BundleAdjuster:
 # drop-in drivers
 # ---------------------------------------------------------------------------
 def euclid_obs_adjuster(K, m, n, obs_pt, obs_cam, obs_x, *varargin, num_vis=0.0, device=0,
-                        rank=0, world_size=1, comm_id=None, semantics="mex", **solver):
+                        rank=0, world_size=1, comm_id=None, semantics="mex", loss="none",
+                        loss_scale=0.0, **solver):
     """The BundleAdjuster that bundle_euclid_obs would create for this problem
     and these options (its structure only: no parameter values), so a caller
     can build it ahead of time -- the host plan of vlgba_create runs with the
@@ -456,14 +498,16 @@ def euclid_obs_adjuster(K, m, n, obs_pt, obs_cam, obs_x, *varargin, num_vis=0.0,
                         fix_structure=o["fix_structure"], fix_motion=o["fix_motion"],
                         pivot=o["pivot"] if o["fix_pivot"] else None, verbose=o["verbose"],
                         num_vis=num_vis, device=device, rank=rank, world_size=world_size,
-                        comm_id=comm_id, semantics=semantics, **solver)
+                        comm_id=comm_id, semantics=semantics, loss=loss, loss_scale=loss_scale,
+                        **solver)
     ba.fingerprint = _adjuster_fingerprint(K, m, n, obs_pt, obs_cam, obs_x, o, num_vis,
-                                           semantics, rank, world_size, device, comm_id)
+                                           semantics, rank, world_size, device, comm_id,
+                                           loss, loss_scale)
     return ba
 
 
 def _adjuster_fingerprint(K, m, n, obs_pt, obs_cam, obs_x, o, num_vis, semantics, rank,
-                          world_size, device, comm_id):
+                          world_size, device, comm_id, loss="none", loss_scale=0.0):
     """What a prebuilt adjuster was made for: sizes, the parsed
     options, K, a hash of the observation list, the device and the RCCL id
     -- a context built for another subset, other options, another GPU or
@@ -487,13 +531,16 @@ def _adjuster_fingerprint(K, m, n, obs_pt, obs_cam, obs_x, o, num_vis, semantics
     return (int(m), int(n), int(o["num_variableK"]), bool(o["fix_structure"]),
             bool(o["fix_motion"]), bool(o["fix_pivot"]), bool(o["verbose"]), float(num_vis),
             semantics, int(rank), int(world_size), int(device), comm_id is not None,
-            h.hexdigest())
+            h.hexdigest(), str(loss), float(loss_scale) if loss != "none" else 0.0)
 
 
 def bundle_euclid_obs(K, Te, w, Xe, obs_pt, obs_cam, obs_x, *varargin, num_vis=0.0, device=0,
                       rank=0, world_size=1, comm_id=None, return_stats=False,
-                      semantics="mex", adjuster=None, return_covariance=False, **solver):
+                      semantics="mex", adjuster=None, return_covariance=False, loss="none",
+                      loss_scale=0.0, **solver):
     """bundle_euclid on a COO observation list (0-based point / camera ids).
+    ``loss`` / ``loss_scale``: the robust loss (BundleAdjuster); error_ is then
+    the robust cost / num_vis, and a returned covariance is the unscaled one.
     ``solver`` keywords go to BundleAdjuster (parity, stop_rel, max_iter,
     max_iter2, lambda0, solver, ordered, schur_kernel).  ``adjuster``: a handle
     made beforehand by euclid_obs_adjuster for the same problem and options
@@ -513,7 +560,7 @@ def bundle_euclid_obs(K, Te, w, Xe, obs_pt, obs_cam, obs_x, *varargin, num_vis=0
             raise ValueError("bundle_euclid_obs: solver options belong to the prebuilt adjuster")
         ba = adjuster.result() if hasattr(adjuster, "result") else adjuster
         want = _adjuster_fingerprint(K, m, n, obs_pt, obs_cam, obs_x, o, num_vis, semantics,
-                                     rank, world_size, device, comm_id)
+                                     rank, world_size, device, comm_id, loss, loss_scale)
         if getattr(ba, "fingerprint", None) != want:
             ba.close()
             raise ValueError("bundle_euclid_obs: the prebuilt adjuster is for another problem "
@@ -521,14 +568,15 @@ def bundle_euclid_obs(K, Te, w, Xe, obs_pt, obs_cam, obs_x, *varargin, num_vis=0
     else:
         ba = euclid_obs_adjuster(K, m, n, obs_pt, obs_cam, obs_x, *varargin, num_vis=num_vis,
                                  device=device, rank=rank, world_size=world_size,
-                                 comm_id=comm_id, semantics=semantics, **solver)
+                                 comm_id=comm_id, semantics=semantics, loss=loss,
+                                 loss_scale=loss_scale, **solver)
     with ba:
         ba.set_params(a, b)
         err, st = ba.run()
         a, b = ba.get_params()
         if return_covariance:
             ba.set_params(a, b)   # a linearisation of its own at the returned point
-            cov = ba.covariance()
+            cov = ba.covariance(scale=loss == "none")
     # Xe_(4,:): the input's (bundle_euclid.m:267) or ones (bundle_euclid_nomex.m:364)
     out = unpack(K, a, b, np.ones((1, n)) if nomex else Xe[3:4], nvk) + (err,)
     out = out + (st,) if return_stats else out
@@ -536,8 +584,9 @@ def bundle_euclid_obs(K, Te, w, Xe, obs_pt, obs_cam, obs_x, *varargin, num_vis=0
 
 
 def bundle_euclid(K, Te, w, Xe, x, *varargin, device=0, return_stats=False, semantics="mex",
-                  return_covariance=False, **solver):
-    """[K_ Te_ w_ Xe_ error_] = bundle_euclid(K, Te, w, Xe, x, ...)  (bundle_euclid.m:1)."""
+                  return_covariance=False, loss="none", loss_scale=0.0, **solver):
+    """[K_ Te_ w_ Xe_ error_] = bundle_euclid(K, Te, w, Xe, x, ...)  (bundle_euclid.m:1);
+    ``loss`` / ``loss_scale`` as bundle_euclid_obs."""
     x = _F(x)
     m, n = np.shape(w)[1], x.shape[1]
     o = parse_options(m, n, varargin, x=x, nomex=semantics == "nomex")
@@ -560,17 +609,19 @@ def bundle_euclid(K, Te, w, Xe, x, *varargin, device=0, return_stats=False, sema
         k += 1
     return bundle_euclid_obs(K, Te, w, Xe, pt, cam, obs_x, *rest, num_vis=num_vis,
                              device=device, return_stats=return_stats, semantics=semantics,
-                             return_covariance=return_covariance, **solver)
+                             return_covariance=return_covariance, loss=loss,
+                             loss_scale=loss_scale, **solver)
 
 
 def bundle_euclid_nomex(K, Te, w, Xe, x, *varargin, device=0, return_stats=False,
-                        return_covariance=False, **solver):
+                        return_covariance=False, loss="none", loss_scale=0.0, **solver):
     """[K_ Te_ w_ Xe_ error_] = bundle_euclid_nomex(K, Te, w, Xe, x, ...)
     (bundle_euclid_nomex.m:1): the same LM loop with the twin's semantics --
     db from every camera parameter (:268-277), no 'fix_pivot', Xe_(4,:) = 1."""
     return bundle_euclid(K, Te, w, Xe, x, *varargin, device=device,
                          return_stats=return_stats, semantics="nomex",
-                         return_covariance=return_covariance, **solver)
+                         return_covariance=return_covariance, loss=loss,
+                         loss_scale=loss_scale, **solver)
 
 
 def bundle_euclid_resect(K, Te, w, Xs, xs, *varargin, device=0, max_iter=0, max_iter2=0,

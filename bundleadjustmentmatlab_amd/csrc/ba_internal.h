@@ -76,6 +76,13 @@ struct ba_flags {
 // each) / host checks (pairs x arc tiles) in its setup, else the natural order
 #define BA_ND_MAX_PAIRS 16384LL
 #define BA_ND_MAX_SETUP (1LL << 26)
+// robust loss of the fast path (vlgba_set_loss; vlg_loss in ba_kernels.hip):
+// kind 0 none, 1 Huber, 2 Cauchy; c the scale in pixels
+struct ba_loss {
+    int kind;
+    double c;
+};
+
 struct ba_camred {
     const int *cam_eptr, *cam_eslots;
     const double *upart;
@@ -213,6 +220,10 @@ struct ba_dev {
     int mfma;          // fast path: 1 = some MFMA Schur chunks (k_schur_mfma: groups
                        // [0, ngrp_mf)), 0 = term lists only (k_schur_group)
     int no_mfma;       // option: force the term-list Schur kernel
+    // robust loss (fast path only): the kernels' LOSS = true instantiations run
+    // when loss_kind != 0, else the plain ones
+    int loss_kind;
+    double loss_scale;
     int ndb;           // camera parameters in the back substitution: 6 (MEX, App. A
                        // Q3) or NA (bundle_euclid_nomex.m semantics)
     int nch;           // chunks
@@ -342,6 +353,9 @@ int ba_launch_schur(ba_dev *d, double lambda);
 int ba_launch_assemble(ba_dev *d);
 int ba_launch_update(ba_dev *d, double lambda, ba_flags f);
 int ba_launch_yeb(ba_dev *d);
+// per observation (internal order) at the current parameters: e [N][2] = x - x_hat
+// (unweighted), w [N], rho [N] of the context's loss; any pointer may be NULL
+int ba_launch_obs_residuals(ba_dev *d, double *e, double *w, double *rho);
 int ba_launch_publish(ba_dev *d);   // scal[0..5] + ++seq -> hres (host-mapped)
 void *ba_dmalloc(size_t bytes);   // per-device caching allocator (ba_solver.cpp)
 // raise kernel fn's dynamic-LDS limit to >= bytes on the current device (cached

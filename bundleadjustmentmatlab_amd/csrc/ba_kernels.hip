@@ -80,6 +80,38 @@ __device__ __forceinline__ void block_sum_to(double v, double *out)
 }
 
 // -------------------------------------------------------------------------
+// Robust loss of one observation (first-order IRLS): s =
+// e0^2 + e1^2 in pixels^2, c the scale in pixels.  rho(s) is the observation's
+// cost, sqrtw = sqrt(rho'(s)) the factor of its Jacobian rows and residual.
+//   1 Huber   rho = s (s <= c^2), else 2 c sqrt(s) - c^2;  w = 1, else c / sqrt(s)
+//   2 Cauchy  rho = c^2 log1p(s / c^2);                     w = 1 / (1 + s / c^2)
+// The inlier branch of Huber returns s and 1.0 themselves: with every s below
+// c^2 a pass computes the bits of the plain one.
+// -------------------------------------------------------------------------
+__device__ __forceinline__ void vlg_loss(int kind, double c, double s, double *rho,
+                                         double *sqrtw)
+{
+    const double c2 = c * c;
+    if (kind == 1) {
+        if (s <= c2) {
+            *rho = s;
+            *sqrtw = 1.0;
+        } else {
+            const double r = sqrt(s);
+            *rho = 2.0 * c * r - c2;
+            *sqrtw = sqrt(c / r);
+        }
+    } else if (kind == 2) {
+        const double q = s / c2;
+        *rho = c2 * log1p(q);
+        *sqrtw = sqrt(1.0 / (1.0 + q));
+    } else {
+        *rho = s;
+        *sqrtw = 1.0;
+    }
+}
+
+// -------------------------------------------------------------------------
 // The 9 FD columns of [A | B] for fix_calibration (NA = 6), shared by the two
 // lanes of an observation with one instruction stream and the work each
 // column really needs (mex_bundle_1_XABeUVWeAeB.c:14-70, the same
@@ -326,7 +358,11 @@ struct ba_upd {
     const double *dpg_long;
 };
 
-template <int NA, bool UPD>
+// LOSS = true (vlgba_set_loss): the observation's row [A | B | e] times
+// sqrt(w), rho(s) into the chunk's cost partial (vlg_loss); everything after
+// the row -- W, V, eB, the U / eA partials -- is then the weighted normal
+// equations' without another change.  LOSS = false is the plain body.
+template <int NA, bool UPD, bool LOSS>
 __device__ __forceinline__ void linearize_chunk_body(
     const int *__restrict__ ch_pt, const int *__restrict__ ch_obase,
     const int *__restrict__ ch_eslot, const int *__restrict__ eslot_optr,
@@ -338,9 +374,11 @@ __device__ __forceinline__ void linearize_chunk_body(
     double *__restrict__ W, double *__restrict__ V, double *__restrict__ eB,
     double *__restrict__ upart, double *__restrict__ part_sse, int nch_reg,
     const int *__restrict__ seg_pt, double *__restrict__ vseg, const int *__restrict__ ch_cam,
-    ba_upd u, int ch)
+    ba_upd u, int ch, ba_loss ls)
 {
     constexpr int NC0 = (NA + 4) / 2;       // lane 0: base + FD columns [0, NC0)
+    // (LOSS: each lane scales its own columns in place, one lane pair per row)
+    static_assert(!LOSS || 2 * BA_CH_OBS >= 256, "one lane pair per LDS row");
     constexpr int RS = 2 * NA + 8;          // LDS row: A (2 NA), B (6), e (2)
     constexpr int NU = NA * (NA + 1) / 2;
     static_assert(BA_CH_OBS + 1 <= 256 && BA_CH_PTS + 1 <= 256, "one metadata word per lane");
@@ -600,7 +638,29 @@ __device__ __forceinline__ void linearize_chunk_body(
                     }
                 }
             }
-            if (!half) {
+            if constexpr (LOSS) {
+                // both lanes of the pair hold xh: each forms e, s and sqrt(w) and
+                // scales the columns it wrote (NA = 6, fd_columns_6: lane 0
+                // columns 0 1 2 3 5, lane 1 columns 4 6 7 8), lane 0 also e
+                const double e0 = obs_x[2 * (size_t)o] - xh[0];
+                const double e1 = obs_x[2 * (size_t)o + 1] - xh[1];
+                double rho, sw;
+                vlg_loss(ls.kind, ls.c, e0 * e0 + e1 * e1, &rho, &sw);
+#pragma unroll
+                for (int col = 0; col < NA + 3; col++) {
+                    const bool lane1 = NA == 6 ? (col == 4 || col > 5) : col >= NC0;
+                    if (lane1 == (half != 0)) {
+                        row[2 * col] *= sw;
+                        row[2 * col + 1] *= sw;
+                    }
+                }
+                if (!half) {
+                    row[2 * NA + 6] = e0 * sw;
+                    row[2 * NA + 7] = e1 * sw;
+                    if (live) sse = rho;
+                    wz[lo] = f.fix_structure || f.fix_motion || (f.has_pivot && pivot[j]);
+                }
+            } else if (!half) {
                 const double e0 = obs_x[2 * (size_t)o] - xh[0];
                 const double e1 = obs_x[2 * (size_t)o + 1] - xh[1];
                 row[2 * NA + 6] = e0;
@@ -737,7 +797,15 @@ __device__ __forceinline__ void linearize_chunk_body(
 template <int NA>
 __global__ __launch_bounds__(256, (NA == 6) ? BA_LIN_WAVES : 1) void k_linearize_chunk(BA_LIN_ARGS)
 {
-    linearize_chunk_body<NA, false>(BA_LIN_PASS, ba_upd{}, blockIdx.x);
+    linearize_chunk_body<NA, false, false>(BA_LIN_PASS, ba_upd{}, blockIdx.x, ba_loss{});
+}
+
+// ... with a robust loss (LOSS = true; the host picks the instantiation)
+template <int NA>
+__global__ __launch_bounds__(256, (NA == 6) ? BA_LIN_WAVES : 1) void k_linearize_chunk_loss(
+    BA_LIN_ARGS, ba_loss ls)
+{
+    linearize_chunk_body<NA, false, true>(BA_LIN_PASS, ba_upd{}, blockIdx.x, ls);
 }
 
 // the fused update: the point update of the pass, then the linearisation at
@@ -747,7 +815,14 @@ template <int NA>
 __global__ __launch_bounds__(256, (NA == 6) ? BA_LIN_WAVES : 1) void k_update_linearize(BA_LIN_ARGS,
                                                                              ba_upd u)
 {
-    linearize_chunk_body<NA, true>(BA_LIN_PASS, u, blockIdx.x);
+    linearize_chunk_body<NA, true, false>(BA_LIN_PASS, u, blockIdx.x, ba_loss{});
+}
+
+template <int NA>
+__global__ __launch_bounds__(256, (NA == 6) ? BA_LIN_WAVES : 1) void k_update_linearize_loss(
+    BA_LIN_ARGS, ba_upd u, ba_loss ls)
+{
+    linearize_chunk_body<NA, true, true>(BA_LIN_PASS, u, blockIdx.x, ls);
 }
 
 // U_j, eA_j from the per-chunk partials (fast path).  One 256-lane workgroup
@@ -2037,19 +2112,27 @@ __global__ __launch_bounds__(256) void k_point_update(
 //   lane per obs:   new projection with a_new, b_new, new SSE     (:149-166)
 // SSE / dpg partials per chunk, summed in chunk order by k_sum_parts.
 // -------------------------------------------------------------------------
-template <int NA>
-__global__ __launch_bounds__(256) void k_point_update_chunk(
-    const int *__restrict__ ch_pt, const int *__restrict__ ch_obase,
-    const int *__restrict__ pt_ptr, const int *__restrict__ obs_cam,
-    const unsigned char *__restrict__ obs_lpt, const double *__restrict__ obs_x,
-    const double *__restrict__ K4, const double *__restrict__ W,
-    const double *__restrict__ da, const double *__restrict__ eB,
-    const double *__restrict__ Vinv, const double *__restrict__ b,
-    const double *__restrict__ a_new, const double *__restrict__ rot_new, int ndb,
-    double lambda, double *__restrict__ db, double *__restrict__ b_new,
-    double *__restrict__ part_sse, double *__restrict__ part_dpg, int nch_reg,
-    const int *__restrict__ seg_pt, const int *__restrict__ seg_long,
-    const int *__restrict__ long_o0, const double *__restrict__ dpg_long)
+#define BA_PUC_ARGS                                                                        \
+    const int *__restrict__ ch_pt, const int *__restrict__ ch_obase,                       \
+        const int *__restrict__ pt_ptr, const int *__restrict__ obs_cam,                   \
+        const unsigned char *__restrict__ obs_lpt, const double *__restrict__ obs_x,       \
+        const double *__restrict__ K4, const double *__restrict__ W,                       \
+        const double *__restrict__ da, const double *__restrict__ eB,                      \
+        const double *__restrict__ Vinv, const double *__restrict__ b,                     \
+        const double *__restrict__ a_new, const double *__restrict__ rot_new, int ndb,     \
+        double lambda, double *__restrict__ db, double *__restrict__ b_new,                \
+        double *__restrict__ part_sse, double *__restrict__ part_dpg, int nch_reg,         \
+        const int *__restrict__ seg_pt, const int *__restrict__ seg_long,                  \
+        const int *__restrict__ long_o0, const double *__restrict__ dpg_long
+#define BA_PUC_PASS                                                                        \
+    ch_pt, ch_obase, pt_ptr, obs_cam, obs_lpt, obs_x, K4, W, da, eB, Vinv, b, a_new, rot_new, \
+        ndb, lambda, db, b_new, part_sse, part_dpg, nch_reg, seg_pt, seg_long, long_o0,    \
+        dpg_long
+
+// LOSS = true: the new cost is the sum of rho(s) (vlg_loss), as the
+// linearisation's; W, eB and V*^-1 are already the weighted ones
+template <int NA, bool LOSS>
+__device__ __forceinline__ void point_update_chunk_body(BA_PUC_ARGS, ba_loss ls)
 {
     __shared__ double wl[BA_CH_OBS * 3 * NA];   // the chunk's W rows, then t_o
     __shared__ double bn[BA_CH_PTS * 3];
@@ -2093,6 +2176,10 @@ __global__ __launch_bounds__(256) void k_point_update_chunk(
             const double d0 = obs_x[2 * (size_t)o] - xh[0];
             const double d1 = obs_x[2 * (size_t)o + 1] - xh[1];
             sse = d0 * d0 + d1 * d1;
+            if constexpr (LOSS) {
+                double sw;
+                vlg_loss(ls.kind, ls.c, sse, &sse, &sw);
+            }
         }
         block_sum_to<256>(sse, part_sse + ch);
         __syncthreads();
@@ -2199,10 +2286,67 @@ __global__ __launch_bounds__(256) void k_point_update_chunk(
         const double d0 = ox0 - xh[0];
         const double d1 = ox1 - xh[1];
         sse = d0 * d0 + d1 * d1;
+        if constexpr (LOSS) {
+            double sw;
+            vlg_loss(ls.kind, ls.c, sse, &sse, &sw);
+        }
     }
     block_sum_to<256>(sse, part_sse + ch);
     __syncthreads();
     block_sum_to<256>(dpg, part_dpg + ch);
+}
+
+template <int NA>
+__global__ __launch_bounds__(256) void k_point_update_chunk(BA_PUC_ARGS)
+{
+    point_update_chunk_body<NA, false>(BA_PUC_PASS, ba_loss{});
+}
+
+template <int NA>
+__global__ __launch_bounds__(256) void k_point_update_chunk_loss(BA_PUC_ARGS, ba_loss ls)
+{
+    point_update_chunk_body<NA, true>(BA_PUC_PASS, ls);
+}
+
+// -------------------------------------------------------------------------
+// vlgba_get_residuals: per observation (one lane each) the unweighted residual
+// e = x - x_hat at (a, b) -- the linearisation's base projection, the same
+// code -- and the loss's weight w = sqrtw^2 and cost rho (vlg_loss; none: 1
+// and s).  On demand only: the passes store nothing per observation.
+// -------------------------------------------------------------------------
+template <int NA>
+__global__ __launch_bounds__(256) void k_obs_residuals(
+    const int *__restrict__ pt_ptr, const int *__restrict__ obs_cam,
+    const double *__restrict__ obs_x, const double *__restrict__ K4,
+    const double *__restrict__ a, const double *__restrict__ rot,
+    const double *__restrict__ b, int n, int N, ba_loss ls, double *__restrict__ e,
+    double *__restrict__ w, double *__restrict__ rho)
+{
+    const int o = blockIdx.x * 256 + threadIdx.x;
+    if (o >= N) return;
+    // the observation's point: pt_ptr[i] <= o < pt_ptr[i + 1]
+    int i = 0, hi = n;
+    while (hi - i > 1) {
+        const int mid = i + ((hi - i) >> 1);
+        if (pt_ptr[mid] <= o) i = mid;
+        else hi = mid;
+    }
+    const int j = obs_cam[o];
+    double bi[3], xh[2];
+#pragma unroll
+    for (int c = 0; c < 3; c++) bi[c] = b[3 * (size_t)i + c];
+    cam_view<NA> cv(a, K4, rot, j);
+    cv.project(bi, xh);
+    const double e0 = obs_x[2 * (size_t)o] - xh[0];
+    const double e1 = obs_x[2 * (size_t)o + 1] - xh[1];
+    double r, sw;
+    vlg_loss(ls.kind, ls.c, e0 * e0 + e1 * e1, &r, &sw);
+    if (e) {
+        e[2 * (size_t)o] = e0;
+        e[2 * (size_t)o + 1] = e1;
+    }
+    if (w) w[o] = sw * sw;
+    if (rho) rho[o] = r;
 }
 
 // -------------------------------------------------------------------------
@@ -2419,11 +2563,22 @@ static void lin_chunk_launch(ba_dev *d, ba_flags f, const double *a, const doubl
                              const double *b, double *W, double *V, double *eB, double *upart,
                              double *chsse, const ba_upd *u)
 {
-    if (u)
+    const ba_loss ls{d->loss_kind, d->loss_scale};
+    if (u && ls.kind)
+        k_update_linearize_loss<NA><<<d->nch, 256, 0, d->stream>>>(
+            d->ch_pt, d->ch_obase, d->ch_eslot, d->eslot_optr, d->eslot_obs, d->pt_ptr,
+            d->obs_cam, d->obs_lpt, d->obs_x, d->K4, a, rot, b, f, d->pivot, W, V, eB, upart,
+            chsse, d->nch_reg, d->seg_pt, d->vseg, d->ch_cam, *u, ls);
+    else if (u)
         k_update_linearize<NA><<<d->nch, 256, 0, d->stream>>>(
             d->ch_pt, d->ch_obase, d->ch_eslot, d->eslot_optr, d->eslot_obs, d->pt_ptr,
             d->obs_cam, d->obs_lpt, d->obs_x, d->K4, a, rot, b, f, d->pivot, W, V, eB, upart,
             chsse, d->nch_reg, d->seg_pt, d->vseg, d->ch_cam, *u);
+    else if (ls.kind)
+        k_linearize_chunk_loss<NA><<<d->nch, 256, 0, d->stream>>>(
+            d->ch_pt, d->ch_obase, d->ch_eslot, d->eslot_optr, d->eslot_obs, d->pt_ptr,
+            d->obs_cam, d->obs_lpt, d->obs_x, d->K4, a, rot, b, f, d->pivot, W, V, eB, upart,
+            chsse, d->nch_reg, d->seg_pt, d->vseg, d->ch_cam, ls);
     else
         k_linearize_chunk<NA><<<d->nch, 256, 0, d->stream>>>(
             d->ch_pt, d->ch_obase, d->ch_eslot, d->eslot_optr, d->eslot_obs, d->pt_ptr,
@@ -2711,12 +2866,24 @@ int ba_launch_update(ba_dev *d, double lambda, ba_flags f)
                                    d->long_pt, d->long_o0, d->obs_cam, d->W, d->da, d->eB,
                                    d->Vinv, d->b, d->ndb, lambda, d->db, d->b_new,
                                    d->dpg_long)));
-        BA_DISPATCH(d->na, (k_point_update_chunk<NA><<<d->nch, 256, 0, d->stream>>>(
-                               d->ch_pt, d->ch_obase, d->pt_ptr, d->obs_cam, d->obs_lpt,
-                               d->obs_x, d->K4, d->W, d->da, d->eB, d->Vinv, d->b, d->a_new,
-                               d->rot_new, d->ndb, lambda, d->db, d->b_new, d->chsse + d->nch,
-                               d->chsse + 2 * (size_t)d->nch, d->nch_reg, d->seg_pt,
-                               d->seg_long, d->long_o0, d->dpg_long)));
+        if (d->loss_kind) {
+            const ba_loss ls{d->loss_kind, d->loss_scale};
+            BA_DISPATCH(d->na, (k_point_update_chunk_loss<NA><<<d->nch, 256, 0, d->stream>>>(
+                                   d->ch_pt, d->ch_obase, d->pt_ptr, d->obs_cam, d->obs_lpt,
+                                   d->obs_x, d->K4, d->W, d->da, d->eB, d->Vinv, d->b,
+                                   d->a_new, d->rot_new, d->ndb, lambda, d->db, d->b_new,
+                                   d->chsse + d->nch, d->chsse + 2 * (size_t)d->nch,
+                                   d->nch_reg, d->seg_pt, d->seg_long, d->long_o0,
+                                   d->dpg_long, ls)));
+        } else {
+            BA_DISPATCH(d->na, (k_point_update_chunk<NA><<<d->nch, 256, 0, d->stream>>>(
+                                   d->ch_pt, d->ch_obase, d->pt_ptr, d->obs_cam, d->obs_lpt,
+                                   d->obs_x, d->K4, d->W, d->da, d->eB, d->Vinv, d->b,
+                                   d->a_new, d->rot_new, d->ndb, lambda, d->db, d->b_new,
+                                   d->chsse + d->nch, d->chsse + 2 * (size_t)d->nch,
+                                   d->nch_reg, d->seg_pt, d->seg_long, d->long_o0,
+                                   d->dpg_long)));
+        }
         KT_E(d, KT_PTUPD);
         // new SSE, point dpg, camera dpg: one launch
         ba_sum3 s3 = {{d->chsse + d->nch, d->chsse + 2 * (size_t)d->nch, d->part},
@@ -2744,6 +2911,16 @@ int ba_launch_update(ba_dev *d, double lambda, ba_flags f)
     KT_E(d, KT_PTUPD);
     k_sum_parts<<<1, BA_SUM_BS, 0, d->stream>>>(d->part + BA_PART_MAX, g, d->scal + 1);
     k_sum_parts<<<1, BA_SUM_BS, 0, d->stream>>>(d->part + 2 * BA_PART_MAX, g, d->scal + 3);
+    return -(int)hipGetLastError();
+}
+
+int ba_launch_obs_residuals(ba_dev *d, double *e, double *w, double *rho)
+{
+    if (d->N <= 0) return 0;
+    const ba_loss ls{d->loss_kind, d->loss_scale};
+    BA_DISPATCH(d->na, (k_obs_residuals<NA><<<(d->N + 255) / 256, 256, 0, d->stream>>>(
+                           d->pt_ptr, d->obs_cam, d->obs_x, d->K4, d->a, d->rot, d->b, d->n,
+                           d->N, ls, e, w, rho)));
     return -(int)hipGetLastError();
 }
 

@@ -2046,6 +2046,8 @@ static int ctx_create(const vlgba_problem *p, const vlgba_options *o, vlgba_ctx 
         c->d.no_mfma = o->schur_kernel == 1;
         c->d.fuse_camred = BA_FUSE_CAMRED;
         c->d.ndb = o->semantics == 1 ? p->num_a : 6;
+        c->d.loss_kind = VLGBA_LOSS_NONE;   // vlgba_set_loss
+        c->d.loss_scale = 0.0;
         rc = ctx_setup(c, p, h, pt_ptr_all, lower_blocks, all_diag, stage_mode);
         if (rc) break;
         ST_MARK("setup_end");
@@ -2956,6 +2958,8 @@ int vlgba_covariance(vlgba_ctx *c, int scale, double *cov_a, double *cov_a_full,
     // one rank only: the sharded form (an all-reduce of S0 and per-rank point
     // blocks) is not built, and no collective runs here
     if (c->world > 1 || c->comm || c->host_allreduce) return VLGBA_E_ARG;
+    // sigma2 from a robust cost is not the noise variance: unscaled only
+    if (scale && c->d.loss_kind) return VLGBA_E_ARG;
     TRY(ctx_enter(c));
     // the call's launches stay out of the pass timers
     const int timing = c->timing;
@@ -2965,6 +2969,64 @@ int vlgba_covariance(vlgba_ctx *c, int scale, double *cov_a, double *cov_a_full,
     const int rc = cov_run(c, scale, cov_a, cov_a_full, cov_b, info);
     c->timing = timing;
     if (c->d.kt) c->d.kt->on = kt_on;
+    return rc;
+}
+
+int vlgba_set_loss(vlgba_ctx *c, int kind, double scale)
+{
+    if (!c || kind < VLGBA_LOSS_NONE || kind > VLGBA_LOSS_CAUCHY) return VLGBA_E_ARG;
+    if (kind != VLGBA_LOSS_NONE && !(std::isfinite(scale) && scale > 0)) return VLGBA_E_ARG;
+    // ordered / parity mode exists for bit parity with a reference that has no loss
+    if (c->d.ordered) return VLGBA_E_ARG;
+    c->d.loss_kind = kind;
+    c->d.loss_scale = kind != VLGBA_LOSS_NONE ? scale : 0.0;
+    c->lin_valid = 0;   // the next pass / getter linearises with the new weights
+    return 0;
+}
+
+int vlgba_get_loss(vlgba_ctx *c, int *kind, double *scale)
+{
+    if (!c) return VLGBA_E_ARG;
+    if (kind) *kind = c->d.loss_kind;
+    if (scale) *scale = c->d.loss_scale;
+    return 0;
+}
+
+int vlgba_get_residuals(vlgba_ctx *c, double *e, double *w, double *rho)
+{
+    if (!c) return VLGBA_E_ARG;
+    TRY(ctx_enter(c));
+    ba_dev &d = c->d;
+    const size_t N = (size_t)d.N;
+    if (N == 0 || (!e && !w && !rho)) return 0;
+    double *buf = nullptr;   // e [N][2] | w [N] | rho [N], internal observation order
+    TRY(dalloc(&buf, 4 * N));
+    auto run = [&]() -> int {
+        // the rotation table of d.a is current (set_params / an accepted step)
+        TRY(ba_launch_obs_residuals(&d, e ? buf : nullptr, w ? buf + 2 * N : nullptr,
+                                    rho ? buf + 3 * N : nullptr));
+        double *dst[3] = {e, w, rho};
+        const size_t off[3] = {0, 2 * N, 3 * N}, wd[3] = {2, 1, 1};
+        std::vector<double> tmp;
+        for (int q = 0; q < 3; q++) {
+            if (!dst[q]) continue;
+            if (c->operm.empty()) {
+                TRY(download(dst[q], buf + off[q], wd[q] * N, d.stream));
+                continue;
+            }
+            tmp.resize(wd[q] * N);   // internal observation order -> input order
+            TRY(download(tmp.data(), buf + off[q], wd[q] * N, d.stream));
+            VLGBA_CHECK(hipStreamSynchronize(d.stream));
+            for (size_t o = 0; o < N; o++)
+                std::memcpy(dst[q] + wd[q] * c->operm[o], tmp.data() + wd[q] * o,
+                            sizeof(double) * wd[q]);
+        }
+        VLGBA_CHECK(hipStreamSynchronize(d.stream));
+        return 0;
+    };
+    const int rc = run();
+    if (rc) (void)hipStreamSynchronize(d.stream);
+    ba_dfree(buf);
     return rc;
 }
 

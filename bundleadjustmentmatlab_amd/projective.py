@@ -74,10 +74,12 @@ def unpack(a, b, Xp4):
 
 def bundle_projective_obs(Pp, Xp, obs_pt, obs_cam, obs_x, *varargin, num_vis=0.0, device=0,
                           rank=0, world_size=1, comm_id=None, return_stats=False,
-                          semantics="mex", return_covariance=False, **solver_kw):
+                          semantics="mex", return_covariance=False, loss="none",
+                          loss_scale=0.0, **solver_kw):
     """bundle_projective on a COO observation list (0-based point / camera ids);
     varargin takes 'fix_structure', 'fix_motion', 'verbose' (visibility is the
-    list itself).  ``return_covariance`` appends BundleAdjuster.covariance()
+    list itself).  ``loss`` / ``loss_scale``: the robust loss (BundleAdjuster;
+    error_ is then the robust cost, a returned covariance the unscaled one).  ``return_covariance`` appends BundleAdjuster.covariance()
     at the returned parameters (the projective model fixes no gauge: expect
     VlgbaError -1007 or very large values unless the structure is fixed)."""
     Pp, Xp = _F(Pp), _F(Xp)
@@ -89,21 +91,22 @@ def bundle_projective_obs(Pp, Xp, obs_pt, obs_cam, obs_x, *varargin, num_vis=0.0
                         fix_structure=o["fix_structure"], fix_motion=o["fix_motion"],
                         verbose=o["verbose"], num_vis=num_vis, device=device, rank=rank,
                         world_size=world_size, comm_id=comm_id, semantics=semantics,
-                        **solver_kw) as ba:
+                        loss=loss, loss_scale=loss_scale, **solver_kw) as ba:
         ba.set_params(a, b)
         err, st = ba.run()
         a, b = ba.get_params()
         if return_covariance:
             ba.set_params(a, b)   # a linearisation of its own at the returned point
-            cov = ba.covariance()
+            cov = ba.covariance(scale=loss == "none")
     out = unpack(a, b, Xp[3:4]) + (err,)
     out = out + (st,) if return_stats else out
     return out + (cov,) if return_covariance else out
 
 
 def bundle_projective(Pp, Xp, x, *varargin, device=0, return_stats=False, semantics="mex",
-                      return_covariance=False, **solver_kw):
-    """[Pp_ Xp_ error_] = bundle_projective(Pp, Xp, x, ...) (bundle_projective.m:1)."""
+                      return_covariance=False, loss="none", loss_scale=0.0, **solver_kw):
+    """[Pp_ Xp_ error_] = bundle_projective(Pp, Xp, x, ...) (bundle_projective.m:1);
+    ``loss`` / ``loss_scale`` as bundle_projective_obs."""
     x, Pp = _F(x), _F(Pp)
     m, n = Pp.shape[2], x.shape[1]
     o = parse_options(m, n, varargin, x=x)
@@ -121,14 +124,16 @@ def bundle_projective(Pp, Xp, x, *varargin, device=0, return_stats=False, semant
         k += 1
     return bundle_projective_obs(Pp, Xp, pt, cam, obs_x, *rest, num_vis=num_vis, device=device,
                                  return_stats=return_stats, semantics=semantics,
-                                 return_covariance=return_covariance, **solver_kw)
+                                 return_covariance=return_covariance, loss=loss,
+                                 loss_scale=loss_scale, **solver_kw)
 
 
-def bundle_projective_nomex(Pp, Xp, x, *varargin, device=0, return_stats=False, **solver_kw):
+def bundle_projective_nomex(Pp, Xp, x, *varargin, device=0, return_stats=False, loss="none",
+                            loss_scale=0.0, **solver_kw):
     """[Pp_ Xp_ error_] = bundle_projective_nomex(Pp, Xp, x, ...)
     (bundle_projective_nomex.m:1): db from all 12 camera parameters (:247-256)."""
     return bundle_projective(Pp, Xp, x, *varargin, device=device, return_stats=return_stats,
-                             semantics="nomex", **solver_kw)
+                             semantics="nomex", loss=loss, loss_scale=loss_scale, **solver_kw)
 
 
 # ---------------------------------------------------------------------------

@@ -36,7 +36,9 @@ extern "C" {
  * VLGBA_NKERNELS 18 (k_update_linearize), vlgba_kernel_flops; 4 =
  * vlgba_debug_dehom; 5 = vlgba_debug_dehom removed, VLGBA_NPLAN 29 (the
  * envelope runner's launch count), vlgba_debug_force_status word 6; 6 =
- * vlgba_covariance, VLGBA_E_SINGULAR.  Callers
+ * vlgba_covariance, VLGBA_E_SINGULAR; 6 also covers the robust-loss entry
+ * points added since (vlgba_set_loss, vlgba_get_loss, vlgba_get_residuals,
+ * VLGBA_LOSS_*: entry points only, no struct changed).  Callers
  * check it once at load time with VLGBA_ABI_CHECK() (the MEX gateways and the Python
  * loader do): the library compares the version and the struct sizes the
  * caller was compiled with against its own and returns 0 or VLGBA_E_ABI. */
@@ -205,7 +207,9 @@ int vlgba_step(vlgba_ctx *ctx, int relinearize, int update_lm, vlgba_step_info *
  * (num_a x m) summed over all ranks; V (3 x 3 x n_local), eB (3 x n_local) and
  * W (num_a x 3 per observation, observations point-major: points ascending,
  * cameras ascending within a point) for this rank's points.  Any pointer may
- * be NULL.  Also marks the linearisation valid for the next vlgba_step. */
+ * be NULL.  Also marks the linearisation valid for the next vlgba_step.
+ * With a loss set (vlgba_set_loss) these are the weighted quantities: every
+ * observation's Jacobian rows and residual times sqrt(w). */
 int vlgba_get_linearization(vlgba_ctx *ctx, double *U, double *eA, double *V, double *eB,
                             double *W);
 /* the LM loop from the context's parameters; error_out / error_cap as
@@ -224,7 +228,8 @@ int vlgba_get_step(vlgba_ctx *ctx, double *da, double *db);
  * bundle_euclid.m:192): the co-visible blocks S_jk, j >= k (num_a x num_a
  * column major each, lower triangle meaningful for j == k; count =
  * vlgba_plan_info [10]) with their camera pairs blk_jk [2 * count], and e_
- * (num_a * m).  Linearises first if the parameters changed.  NULL skips. */
+ * (num_a * m).  Linearises first if the parameters changed.  NULL skips.
+ * With a loss set: the reduced system of the weighted normal equations. */
 int vlgba_get_reduced_system(vlgba_ctx *ctx, int *blk_jk, double *blocks, double *e_);
 /* Posterior covariance at the context's parameters (linearises first if they
  * changed, as vlgba_get_reduced_system does), undamped (lambda = 0), with the
@@ -263,9 +268,45 @@ int vlgba_get_reduced_system(vlgba_ctx *ctx, int *blk_jk, double *blocks, double
  * buffer; cfg3: 288 MB).  A selected inverse on the solver's own factors,
  * which avoids the dense ld^2 step, is not built.
  * The call leaves the LM state as it was: the next vlgba_step gives the same
- * bits as without it, vlgba_get_step still returns the last pass's step. */
+ * bits as without it, vlgba_get_step still returns the last pass's step.
+ * With a loss set (vlgba_set_loss) the unscaled outputs come from the weighted
+ * linearisation and info[0] is the robust cost sum rho(s); scale != 0 then
+ * returns VLGBA_E_ARG: sigma2 from a robust cost is not the noise variance. */
 int vlgba_covariance(vlgba_ctx *ctx, int scale, double *cov_a, double *cov_a_full,
                      double *cov_b, double *info);
+/* ---- robust loss (iteratively reweighted least squares, first order) -----
+ * s = e0^2 + e1^2 of an observation in pixels^2, scale c in pixels, w = rho'(s):
+ *   VLGBA_LOSS_NONE    rho = s                                     w = 1
+ *   VLGBA_LOSS_HUBER   rho = s (s <= c^2), else 2 c sqrt(s) - c^2  w = 1, else c / sqrt(s)
+ *   VLGBA_LOSS_CAUCHY  rho = c^2 log1p(s / c^2)                    w = 1 / (1 + s / c^2)
+ * The observation's Jacobian rows and residual are multiplied by sqrt(w)
+ * where they are formed, so U, V, W, eA, eB are the weighted normal equations
+ * (Gauss-Newton on the robust cost, no second-order correction) and g the
+ * robust gradient; the LM scalars are the robust cost: vlgba_step_info.old_sse
+ * / new_sse hold sum rho(s), rho = (old - new) / dpg.  The accept rule, the
+ * stop rule and error_ (cost / num_vis) keep their form.  Weights are local
+ * to an observation: sharded contexts need no further collective, every rank
+ * sets the same loss.
+ * vlgba_set_loss: VLGBA_E_ARG for an unknown kind, for a non-finite or <= 0
+ * scale when kind != VLGBA_LOSS_NONE, and for a context in ordered or parity
+ * mode (vlgba_options.ordered != 0), whose purpose is bit parity with a
+ * reference that has no loss.  Marks the linearisation stale: the next pass or
+ * getter linearises again.  VLGBA_LOSS_NONE restores the plain solver exactly.
+ * Not covered (they stay plain least squares): vlgba_resect, the
+ * vlgba_mex_bundle_* stage entries and the MATLAB drop-ins, which keep the
+ * reference's option list. */
+#define VLGBA_LOSS_NONE 0
+#define VLGBA_LOSS_HUBER 1
+#define VLGBA_LOSS_CAUCHY 2
+int vlgba_set_loss(vlgba_ctx *ctx, int kind, double scale);
+int vlgba_get_loss(vlgba_ctx *ctx, int *kind, double *scale);
+/* per observation of this rank at the context's current parameters, in the
+ * order of vlgba_get_linearization's W rows (point-major, cameras ascending
+ * within a point): e [2 x N_local] the unweighted residuals x - x_hat, w
+ * [N_local] the loss's weights and rho [N_local] its costs (no loss: w = 1,
+ * rho = s).  Any pointer may be NULL.  Computed on demand (the passes store
+ * nothing per observation); leaves the LM state untouched. */
+int vlgba_get_residuals(vlgba_ctx *ctx, double *e, double *w, double *rho);
 int vlgba_sync(vlgba_ctx *ctx);
 void vlgba_destroy(vlgba_ctx *ctx);
 /* device-kernel timing of the last vlgba_step, milliseconds per phase:
