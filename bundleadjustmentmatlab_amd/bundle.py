@@ -465,7 +465,7 @@ class BundleAdjuster:
                  "tiles", "cr_levels", "cr_elim", "cr_keep", "ordered", "schur_terms",
                  "blob_words", "mfma", "cr_rows", "mfma_groups", "reordered", "long_points",
                  "nd_arcs", "nd_sep_tiles", "solve_flops_factor", "solve_flops_syrk",
-                 "solve_flops_back", "env_runner_runs")
+                 "solve_flops_back", "env_runner_runs", "vinv_fold", "camupd_fold")
 
     def plan_info(self):
         """Execution-plan sizes of this rank (vlgba_plan_info)."""

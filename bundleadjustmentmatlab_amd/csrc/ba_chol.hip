@@ -32,6 +32,7 @@
 // k_sep_reduce, then the separator) when that shortens the chain of columns;
 // the sequential k_chol_seq in parity mode.
 #include "ba_internal.h"
+#include "ba_camera.h"
 
 #include <algorithm>
 #include <atomic>
@@ -2630,6 +2631,13 @@ __device__ __forceinline__ void cr32_publish(unsigned *flag, unsigned epoch, int
 }
 
 
+// the camera update of a back record's own cameras (ba_dev::camupd_fold)
+struct cr32_camupd {
+    const double *a;   // nullptr: none
+    double *a_new, *rot_new;
+    int na, m;
+};
+
 __global__ __launch_bounds__(256) void k_cr32_fused(double *S, long long lds, int TB, long long ld,
                                                     const int *__restrict__ elim,
                                                     const int *__restrict__ frec,
@@ -2637,7 +2645,8 @@ __global__ __launch_bounds__(256) void k_cr32_fused(double *S, long long lds, in
                                                     double *linv, double *crL, double *rhs,
                                                     double *y, double *x, unsigned *flag,
                                                     unsigned long long *xg, unsigned epoch,
-                                                    double *status, cr32_fplan P)
+                                                    double *status, cr32_fplan P,
+                                                    cr32_camupd cu)
 {
     CR32_LDS_DECL;
     CR_ST(0);
@@ -2737,8 +2746,33 @@ __global__ __launch_bounds__(256) void k_cr32_fused(double *S, long long lds, in
     const int w[8] = {fw(Le, e, 0), fw(Le, e, 1), fw(Le, e, 2), 0, 0, 0, 0, 0};
     cr32_wait_flags(flag, 3, w, epoch, status);
     CR_ST(1);
+    // k_camera_update for the tile's own cameras (ba_dev::camupd_fold: x = da in
+    // camera order, a tile = TB / na whole cameras), from x_e in LDS: a_new =
+    // a + da and the five rotations of its table, lane (camera c, rotation k)
+    // of wave 1 -- one Rodrigues chain, on a wave that does not publish the x
+    // granules.  The lane's a is loaded ahead of the record's waits; nothing
+    // in this launch reads a_new or rot_new.
+    const int cl = threadIdx.x & 63, cc0 = cl / 5, ck = cl - 5 * cc0;
+    const int cj = (cu.a ? TB / cu.na : 0) * e + cc0;
+    const bool con = cu.a && (threadIdx.x >> 6) == 1 && cc0 < TB / cu.na && cj < cu.m;
+    double av[10];   // (na <= 10: the Euclidean models)
+    if (con) {
+#pragma unroll
+        for (int cc = 0; cc < 10; cc++)
+            av[cc] = cc < cu.na ? cu.a[(size_t)cu.na * cj + cc] : 0.0;
+    }
     cr32_back_body<true>(sh, e, p, q, nt, TB, ld, linv, crL, y, x, xg, epoch, status);
     CR_ST(2);
+    if (con) {
+#pragma unroll
+        for (int cc = 0; cc < 10; cc++) {
+            if (cc < cu.na) {
+                av[cc] = av[cc] + sh.um[cu.na * cc0 + cc];
+                if (ck == 0) cu.a_new[(size_t)cu.na * cj + cc] = av[cc];
+            }
+        }
+        rotation_k(av, ck, cu.rot_new + 45 * (size_t)cj);
+    }
     CR_ST(3);
 }
 
@@ -3778,6 +3812,7 @@ static int envelope_backward(ba_dev *d, long long L, double *x, int nospin)
 int ba_chol_solve(ba_dev *d, int nospin)
 {
     const int nt = d->nt;
+    d->camupd_done = 0;   // only the one-launch CR below does the camera update
     const size_t smem3 = sizeof(double) * 3 * NB * LP;
     TRY_RC(ba_ensure_dyn_lds((const void *)k_factor_step, smem3));
     TRY_RC(ba_ensure_dyn_lds((const void *)k_cr_factor, smem3));
@@ -3807,10 +3842,15 @@ int ba_chol_solve(ba_dev *d, int nospin)
         P.sofs[nl] = d->crs_ptr_h[nl];
         for (int l = 0; l <= nl; l++) P.eofs[l] = d->cr_eptr_h[l];
         if (++d->back_epoch == 0) d->back_epoch = 1;
+        cr32_camupd cu{};
+        if (d->camupd_fold) {   // the next update launches no k_camera_update
+            cu = cr32_camupd{d->a, d->a_new, d->rot_new, d->na, d->m};
+            d->camupd_done = 1;
+        }
         KT_B(d);
         k_cr32_fused<<<P.b0[nl] + nrec, 256, 0, d->stream>>>(
             d->S, d->lds, d->tb32, d->ld, d->cr_elim, d->crf, d->crs, d->nt32, d->linv, d->crL,
-            d->rhs, d->ywork, d->da, d->crflag, d->xgran, d->back_epoch, d->scal + 4, P);
+            d->rhs, d->ywork, d->da, d->crflag, d->xgran, d->back_epoch, d->scal + 4, P, cu);
         KT_E(d, KT_CR_FACTOR);
         return -(int)hipGetLastError();
     }

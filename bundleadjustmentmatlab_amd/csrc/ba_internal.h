@@ -173,6 +173,16 @@ struct ba_dev {
     // ba_chol_setup): the CR writes only those tiles, so S's other entries
     // keep the zeros of the setup.
     int asm_direct_ok, asm_direct;
+    // camera update inside the one-launch CR (k_cr32_fused, x = da in camera
+    // order, a tile = whole cameras): each back record forms a_new = a + da
+    // and the rotation table of its own cameras from x_e in LDS, and the
+    // update's final sums (k_sum_parts3) form the camera part of dp'(lambda dp
+    // + g) -- so the update that directly follows such a solve launches no
+    // k_camera_update.  camupd_fold: allowed (setup; VLGBA_CAMUPD_FOLD=0: off);
+    // camupd_done: set by the solve that did it, consumed by the next
+    // ba_launch_update (every other solve and every other writer of da clears
+    // it: their update launches k_camera_update).
+    int camupd_fold, camupd_done;
     // one-level nested dissection of the envelope (ba_chol_setup, auto mode
     // when S is not tridiagonal; dense_solve 4 forces it): the cameras split
     // into nd_np arcs of consecutive cameras minus the separator (cameras
@@ -256,6 +266,13 @@ struct ba_dev {
     unsigned char *obs_lpt;           // [N] chunk-local point of each observation
     int max_blob;                     // term groups: largest chunk record
     int ngrp_mf;                      // leading MFMA groups
+    // V*^-1 inside the MFMA Schur launch: each group's workgroup inverts the
+    // damped V of its own points in its prologue, so no k_point_vinv launch.
+    // Needs the MFMA groups' point ranges to tile every point [0, n) (checked
+    // once at setup: no per-term groups, no long tracks; points no camera sees
+    // lie inside the ranges and get their zero block).  VLGBA_VINV_FOLD=0
+    // keeps the launch (A/B, tests).
+    int vinv_fold;
     // long tracks (points [p_long, n), ba_solver.cpp build_plan): segment
     // chunks [nch_reg, nch), their V / eB partials, Schur tiles, update sums
     int nch_reg, nl, p_long;

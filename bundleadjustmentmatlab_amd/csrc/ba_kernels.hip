@@ -1396,9 +1396,9 @@ __global__ __launch_bounds__(256, (NA == 6) ? BA_MF_WAVES : 1) void k_schur_mfma
     const int *__restrict__ grp_ge, const int *__restrict__ ch_pt,
     const int *__restrict__ ch_obase, const int *__restrict__ ch_blob,
     const unsigned *__restrict__ blob, const double *__restrict__ W,
-    const double *__restrict__ Vinv, const double *__restrict__ eB, int nobs_all, int n_all,
+    double *Vinv, const double *__restrict__ eB, int nobs_all, int n_all,
     int gcap, int ecap, double *__restrict__ spart, double *__restrict__ epart, int ngrp,
-    ba_camred cred)
+    ba_camred cred, const double *__restrict__ Vdamp, double lambda)
 {
     // workgroups past the groups: the camera reduction of a relinearised pass
     // (independent of the Schur sums, due before k_schur_reduce), filling the
@@ -1425,6 +1425,48 @@ __global__ __launch_bounds__(256, (NA == 6) ? BA_MF_WAVES : 1) void k_schur_mfma
     const int gs0 = grp_gs[g], ngs = grp_gs[g + 1] - gs0;
     const int ge0 = grp_ge[g], nge = grp_ge[g + 1] - ge0;
     const int rb0 = ch_blob[c0], nrw = ch_blob[c0 + nc] - rb0;
+    if (Vdamp) {
+        // V*^-1 of the group's own points (ba_dev::vinv_fold: the MFMA groups'
+        // ranges tile every point, so no k_point_vinv launch): k_point_vinv's
+        // damped vlg_pinv3 on the same inputs, 256 points a step, their 9-double
+        // rows in and out through the LDS pool (>= 256 x 9 doubles then) before
+        // the accumulators and records below take it: every cache line
+        // requested once.  Vinv is not __restrict__: the barrier ahead of the
+        // chunk loop orders these stores before its loads of them (the same
+        // workgroup, the same CU).
+        const int p0 = ch_pt[c0], p1 = ch_pt[c0 + nc];
+        double t[9];
+        auto rows = [&](int i0) {   // the batch's rows, lane by lane
+            const int cnt = 9 * min(256, p1 - i0);
+            const double *src = Vdamp + 9 * (size_t)i0;
+#pragma unroll
+            for (int u = 0; u < 9; u++) t[u] = tid + 256 * u < cnt ? src[tid + 256 * u] : 0.0;
+        };
+        if (p0 < p1) rows(p0);
+        for (int i0 = p0; i0 < p1; i0 += 256) {
+            const int cnt = 9 * min(256, p1 - i0);
+#pragma unroll
+            for (int u = 0; u < 9; u++) sm[tid + 256 * u] = t[u];
+            __syncthreads();
+            if (i0 + 256 < p1) rows(i0 + 256);   // in flight under this batch's inverses
+            if (i0 + tid < p1) {
+                double vs[9], vi[9];
+#pragma unroll
+                for (int q = 0; q < 9; q++) vs[q] = sm[9 * tid + q];
+#pragma unroll
+                for (int c = 0; c < 3; c++) vs[4 * c] = (1 + lambda) * vs[4 * c];
+                vlg_pinv3(vs, vi);
+#pragma unroll
+                for (int q = 0; q < 9; q++) sm[9 * tid + q] = vi[q];
+            }
+            __syncthreads();
+            double *dst = Vinv + 9 * (size_t)i0;
+#pragma unroll
+            for (int u = 0; u < 9; u++)
+                if (tid + 256 * u < cnt) dst[tid + 256 * u] = sm[tid + 256 * u];
+            __syncthreads();
+        }
+    }
     for (int q = tid; q < ngs * NA * NA; q += 256) gacc[q] = 0.0;
     for (int q = tid; q < nge * NA; q += 256) geacc[q] = 0.0;
     for (int q = tid; q < nrw; q += 256) rec[q] = blob[rb0 + q];
@@ -2474,12 +2516,40 @@ struct ba_sum3 {
     double *hres;
     double seq;
     unsigned *cnt;   // zero between launches (the last block resets it)
+    // optional (the camera update ran inside the solve, ba_dev::camupd_done):
+    // block 2 first forms its own partials part[2][0 .. n[2]) -- the camera
+    // part of dp'(lambda dp + g), one per 64 cameras: k_camera_update's
+    // per-lane expression and wave tree
+    const double *cam_da, *cam_eA;   // cam_da == nullptr: part[2] is given
+    double *cam_part;
+    int cam_m, cam_na;
+    double cam_lambda;
 };
 
 __global__ __launch_bounds__(1024) void k_sum_parts3(ba_sum3 a)
 {
     const double *part = a.part[blockIdx.x];
     const int nparts = a.n[blockIdx.x];
+    if (blockIdx.x == 2 && a.cam_da) {
+        // the short block (one partial per 64 cameras against one per chunk):
+        // wave w forms the partials w, w + 16, ...; the barrier orders the
+        // stores before this workgroup's loads of them below
+        const int lane = threadIdx.x & 63;
+        for (int g = threadIdx.x >> 6; g < nparts; g += 16) {
+            const int j = 64 * g + lane;
+            double acc = 0.0;
+            if (j < a.cam_m) {
+                for (int c = 0; c < a.cam_na; c++) {
+                    const double d = a.cam_da[(size_t)a.cam_na * j + c];
+                    acc += d * (a.cam_lambda * d + a.cam_eA[(size_t)a.cam_na * j + c]);
+                }
+            }
+#pragma unroll
+            for (int off = 32; off > 0; off >>= 1) acc += __shfl_down(acc, off, 64);
+            if (lane == 0) a.cam_part[g] = acc;
+        }
+        __syncthreads();
+    }
     double v0 = 0.0, v1 = 0.0, v2 = 0.0, v3 = 0.0;
     int q = threadIdx.x;
     for (; q + 3 * 1024 < nparts; q += 4 * 1024) {
@@ -2666,12 +2736,18 @@ static int launch_schur_fast(ba_dev *d, double lambda)
     const bool two = BA_SCHUR_TWO_STREAMS && d->ngrp_mf > 0 && d->ngrp > d->ngrp_mf &&
                      !d->join_pending && d->side && !(d->kt && d->kt->on);
     if (d->ngrp_mf > 0) {
-        KT_B(d);
-        k_point_vinv<NA><<<(d->n + 255) / 256, 256, 0, d->stream>>>(d->V, d->n, lambda, d->Vinv);
-        KT_E(d, KT_DAMP);
+        // vinv_fold: every point's V*^-1 is formed by its own MFMA group
+        if (!d->vinv_fold) {
+            KT_B(d);
+            k_point_vinv<NA><<<(d->n + 255) / 256, 256, 0, d->stream>>>(d->V, d->n, lambda,
+                                                                        d->Vinv);
+            KT_E(d, KT_DAMP);
+        }
         if (two) VLGBA_CHECK(hipEventRecord(d->ev_fork, d->stream));   // V*^-1 ready
-        const size_t sm2 = sizeof(double) * (d->mf_max_s * NA * NA + d->mf_max_e * NA) +
-                           sizeof(unsigned) * (size_t)d->mf_max_blob;
+        size_t sm2 = sizeof(double) * (d->mf_max_s * NA * NA + d->mf_max_e * NA) +
+                     sizeof(unsigned) * (size_t)d->mf_max_blob;
+        if (d->vinv_fold && sm2 < sizeof(double) * 256 * 9)   // the V rows' stage
+            sm2 = sizeof(double) * 256 * 9;
         TRY_RC(ba_ensure_dyn_lds((const void *)k_schur_mfma<NA>, sm2));
         const int ncr = d->camred_pending ? d->m + 1 : 0;
         d->camred_pending = 0;
@@ -2679,7 +2755,7 @@ static int launch_schur_fast(ba_dev *d, double lambda)
         k_schur_mfma<NA><<<d->ngrp_mf + ncr, 256, sm2, d->stream>>>(
             d->grp_ch, d->grp_gs, d->grp_ge, d->ch_pt, d->ch_obase, d->ch_blob, d->blob, d->W,
             d->Vinv, d->eB, d->N, d->n, d->mf_max_s, d->mf_max_e, d->spart, d->epart,
-            d->ngrp_mf, d->camred);
+            d->ngrp_mf, d->camred, d->vinv_fold ? d->V : nullptr, lambda);
         KT_E(d, KT_SCHUR_MF);
     }
     if (d->ngrp > d->ngrp_mf) {
@@ -2809,15 +2885,28 @@ int ba_launch_assemble(ba_dev *d)
 // SSE is the sum of the new linearisation's per-chunk SSE partials.  lm_apply
 // swaps the buffers when the step is accepted; a rejected step keeps the
 // pass's own linearisation (App. A Q12).
-static int launch_update_fused(ba_dev *d, double lambda, ba_flags f)
+// k_sum_parts3's third block forms the camera partials itself (ba_sum3::cam_da)
+static void sum3_camera_dpg(ba_dev *d, double lam_dpg, ba_sum3 *s3)
+{
+    s3->cam_da = d->da;
+    s3->cam_eA = d->eA;
+    s3->cam_part = d->part;
+    s3->cam_m = d->m;
+    s3->cam_na = d->na;
+    s3->cam_lambda = lam_dpg;
+}
+
+static int launch_update_fused(ba_dev *d, double lambda, ba_flags f, bool folded)
 {
     const int gc = (d->m + 63) / 64;
-    KT_B(d);
     const double lam_dpg = d->dpg_lambda ? lambda : 0.0;
-    BA_DISPATCH(d->na, (k_camera_update<NA><<<gc, 320, 0, d->stream>>>(
-                           d->a, d->da, d->eA, d->m, lam_dpg, d->a_new, d->rot_new,
-                           d->part)));
-    KT_E(d, KT_CAMUPD);
+    if (!folded) {   // (folded: a_new and rot_new are the solve's, ba_dev::camupd_done)
+        KT_B(d);
+        BA_DISPATCH(d->na, (k_camera_update<NA><<<gc, 320, 0, d->stream>>>(
+                               d->a, d->da, d->eA, d->m, lam_dpg, d->a_new, d->rot_new,
+                               d->part)));
+        KT_E(d, KT_CAMUPD);
+    }
     KT_B(d);
     if (d->nl > 0)   // long tracks: db, b_new, dp'g over all their observations
         BA_DISPATCH(d->na, (k_long_db<NA><<<d->nl, 256, 0, d->stream>>>(
@@ -2837,6 +2926,7 @@ static int launch_update_fused(ba_dev *d, double lambda, ba_flags f)
                   {d->nch, d->nch, gc},
                   {d->scal + 1, d->scal + 3, d->scal + 2},
                   d->scal, nullptr, 0.0, d->pub_cnt};
+    if (folded) sum3_camera_dpg(d, lam_dpg, &s3);
     if (d->publish_req) {
         d->seq++;
         s3.hres = d->hres_dev;
@@ -2850,16 +2940,24 @@ static int launch_update_fused(ba_dev *d, double lambda, ba_flags f)
 
 int ba_launch_update(ba_dev *d, double lambda, ba_flags f)
 {
-    if (d->fused) return launch_update_fused(d, lambda, f);
+    // the camera update of the one-launch CR that ran directly before
+    // (ba_dev::camupd_done; consumed here), on the paths whose final sums are
+    // k_sum_parts3 -- every other update launches k_camera_update
+    const bool chunked = !d->ordered && d->nch > 0 && !d->obs_vis && !d->xh_out;
+    const bool folded = d->camupd_done && (d->fused || chunked);
+    d->camupd_done = 0;
+    if (d->fused) return launch_update_fused(d, lambda, f, folded);
     const int gc = (d->m + 63) / 64;
-    KT_B(d);
     // lambda dp'dp once over the ranks (each adds da' eA of its partial eA)
     const double lam_dpg = d->dpg_lambda ? lambda : 0.0;
-    BA_DISPATCH(d->na, (k_camera_update<NA><<<gc, 320, 0, d->stream>>>(
-                           d->a, d->da, d->eA, d->m, lam_dpg, d->a_new, d->rot_new,
-                           d->part)));
-    KT_E(d, KT_CAMUPD);
-    if (!d->ordered && d->nch > 0 && !d->obs_vis && !d->xh_out) {
+    if (!folded) {
+        KT_B(d);
+        BA_DISPATCH(d->na, (k_camera_update<NA><<<gc, 320, 0, d->stream>>>(
+                               d->a, d->da, d->eA, d->m, lam_dpg, d->a_new, d->rot_new,
+                               d->part)));
+        KT_E(d, KT_CAMUPD);
+    }
+    if (chunked) {
         KT_B(d);
         if (d->nl > 0)   // long tracks: db, b_new, dp'g over all their observations
             BA_DISPATCH(d->na, (k_long_db<NA><<<d->nl, 256, 0, d->stream>>>(
@@ -2890,6 +2988,7 @@ int ba_launch_update(ba_dev *d, double lambda, ba_flags f)
                       {d->nch, d->nch, gc},
                       {d->scal + 1, d->scal + 3, d->scal + 2},
                       d->scal, nullptr, 0.0, d->pub_cnt};
+        if (folded) sum3_camera_dpg(d, lam_dpg, &s3);
         if (d->publish_req) {
             d->seq++;
             s3.hres = d->hres_dev;

@@ -1756,6 +1756,21 @@ static int ctx_setup(vlgba_ctx *c, const vlgba_problem *p, const host_obs &h,
         d.mf_max_blob = plan.mf_max_blob;
         d.mf_max_s = plan.mf_max_s;
         d.mf_max_e = plan.mf_max_e;
+        {
+            // V*^-1 inside k_schur_mfma (ba_dev::vinv_fold): the MFMA groups are
+            // the only Schur groups and their point ranges, each the chunks
+            // ch_pt[grp_ch[g]] .. ch_pt[grp_ch[g + 1]], follow one another from
+            // point 0 to point n
+            bool tile = d.ngrp_mf > 0 && d.ngrp == d.ngrp_mf && d.nl == 0;
+            int at = 0;
+            for (int g = 0; tile && g < d.ngrp_mf; g++) {
+                tile = plan.ch_pt[plan.grp_ch[g]] == at &&
+                       plan.ch_pt[plan.grp_ch[g + 1]] >= at;
+                at = plan.ch_pt[plan.grp_ch[g + 1]];
+            }
+            const char *vf = std::getenv("VLGBA_VINV_FOLD");   // read per context (tests)
+            d.vinv_fold = tile && at == d.n && !(vf && vf[0] == '0');
+        }
         pb.add(&d.blob, plan.blob);
         pb.add(&d.ch_blob, plan.ch_blob);
         pb.add(&d.ch_obase, plan.ch_obase);
@@ -1859,6 +1874,15 @@ static int ctx_setup(vlgba_ctx *c, const vlgba_problem *p, const host_obs &h,
         d.asm_direct = d.asm_direct_ok && !(ad && ad[0] == '0') && fast && !d.ordered &&
                        c->world == 1 && !c->comm && d.nl == 0 && d.cr_nlev > 0 && d.cr32 &&
                        d.nd_np == 0;
+        // camera update inside the one-launch CR (ba_dev::camupd_fold): x = da
+        // in camera order, every tile a whole number of cameras, the Euclidean
+        // models' rotation table, the fast path's final sums (k_sum_parts3);
+        // VLGBA_CAMUPD_FOLD=0 keeps k_camera_update (A/B, tests)
+        const char *cf = std::getenv("VLGBA_CAMUPD_FOLD");
+        d.camupd_fold = !(cf && cf[0] == '0') && fast && !d.ordered && d.nch > 0 &&
+                        d.cr_nlev > 0 && d.cr32 && d.cr_fused && d.crflag && d.nd_np == 0 &&
+                        na != BA_PROJ_NA && na <= 10 && d.tb32 % na == 0 &&
+                        d.ld == (long long)na * p->m;
     } else {
         TRY(ctx_alloc(c, &d.da, (size_t)d.lds));
     }
@@ -2286,6 +2310,7 @@ static int nd_natural_retry(vlgba_ctx *c, double lam, double hs[6])
                       c->pinv_e, (rocblas_int)ld) != rocblas_status_success)
             return VLGBA_E_ARG;
     }
+    d.camupd_done = 0;   // (da is not the one-launch CR's)
     VLGBA_CHECK(hipMemcpyAsync(d.da, c->pinv_e, sizeof(double) * ld, hipMemcpyDeviceToDevice,
                                d.stream));
     d.publish_req = 0;
@@ -2328,6 +2353,7 @@ static int pinv_fallback(vlgba_ctx *c, double lam, double hs[6])
         if (info != 0) return VLGBA_E_ARG;   // the eigensolver did not converge
     }
     TRY(ba_pinv_apply(&d, c->pinv_S, c->pinv_ev, ld, d.rhs, c->pinv_w, d.da));
+    d.camupd_done = 0;   // (da is not the one-launch CR's)
     d.publish_req = 0;
     d.published = 0;
     TRY(ba_launch_update(&d, lam, c->flags));
@@ -3146,7 +3172,8 @@ int vlgba_plan_info(vlgba_ctx *c, long long *info, int len)
                                       d.ngrp_mf, c->pperm.empty() ? 0 : 1, d.nl, d.nd_np,
                                       d.nd_np ? d.nt - d.nd_a0[d.nd_np] : 0,
                                       (long long)d.fl_factor, (long long)d.fl_syrk,
-                                      (long long)d.fl_back, d.runner_runs};
+                                      (long long)d.fl_back, d.runner_runs, d.vinv_fold,
+                                      d.camupd_fold};
     for (int k = 0; k < len && k < VLGBA_NPLAN; k++) info[k] = v[k];
     return VLGBA_NPLAN;
 }
@@ -3431,6 +3458,7 @@ static int mex3_impl(int model, int m, int n, int num_a, const double *W, const 
         if ((rc = ctx_alloc(c, &d.obs_vis, (size_t)N))) break;
         if ((rc = upload(d.obs_vis, ov.data(), ov.size(), d.stream))) break;
         if ((rc = upload(d.W, hW.data(), hW.size(), d.stream))) break;
+        d.camupd_done = 0;
         if ((rc = upload(d.da, da, (size_t)d.ld, d.stream))) break;
         if ((rc = upload(d.eB, eB, 3 * (size_t)n, d.stream))) break;
         if ((rc = upload(d.Vinv, Vinv, 9 * (size_t)n, d.stream))) break;

@@ -347,8 +347,14 @@ const char *vlgba_kernel_name(int k);
  * separator SYRK (k_syrk) [27] in the backward solve (k_backward / k_cr_back):
  * tile-dense potrf + trtri, GEMMs and GEMVs, each counted once [28] envelope
  * runner launches (k_env_runner, opt-in VLGBA_ENV_RUNNER=1) made by this
- * context so far.  Writes min(len, VLGBA_NPLAN) entries, returns VLGBA_NPLAN. */
-#define VLGBA_NPLAN 29
+ * context so far [29] 1: the MFMA Schur launch forms V*^-1 itself (no
+ * k_point_vinv launch; VLGBA_VINV_FOLD=0 or a plan whose MFMA groups do not
+ * tile every point: 0) [30] 1: the one-launch cyclic reduction does the camera
+ * update (no k_camera_update launch after it; VLGBA_CAMUPD_FOLD=0 or another
+ * solver: 0).  Writes min(len, VLGBA_NPLAN) entries, returns
+ * VLGBA_NPLAN (a caller built for fewer entries keeps working: entries are
+ * only ever appended, without an ABI bump). */
+#define VLGBA_NPLAN 31
 int vlgba_plan_info(vlgba_ctx *ctx, long long *info, int len);
 
 /* ---- stage entries with the reference MEX argument layouts ---------------
