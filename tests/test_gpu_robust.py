@@ -31,7 +31,9 @@ Every test prints its figures before it asserts (lines starting ROBUST, pytest -
 Measured on an MI355X; no bar was widened.  Largest |diff| / bound of the stage
 check over all its cases: U 0.073, eA 0.11, V 0.15, eB 0.15, W 0.25, w 0.23,
 rho 0.36, the cost 0.001 (Huber and Cauchy alike; the largest U and eA on the
-140-camera point).  Converged Cauchy cost 1.871022836, the reference's robust LM
+140-camera point).  The ladders of tests/track_scenes.py (tracks of up to 257 /
+273 / 280 views in three segments, num_a 7 / 10 / 12, Huber): U 0.10, eA 0.070,
+V 0.11, eB 0.14, W 0.22, w 0.21, rho 0.23, the cost 0.0002.  Converged Cauchy cost 1.871022836, the reference's robust LM
 from there 1.871022758 (drop 4.2e-8).  End to end: inlier RMS 4.9 px after the
 plain solve, 0.61 px after the Cauchy solve; largest weight of a planted outlier
 0.0098; every inlier above 0.5 (the reference on the CPU: 4.895, 0.6143, 0.0098,
@@ -84,7 +86,13 @@ def _ladybug():
     return sc, sc.obs_pt, sc.obs_cam, sc.obs_x
 
 
+LADDER_TOP = {7: 257, 10: 273, 12: 280}     # as tests/test_gpu_track_lengths.py
+
+
 def _scene(name, na):
+    if name == "ladder":    # tests/track_scenes.py: up to three full segments per track
+        import track_scenes as ts
+        return ts.ladder(na, LADDER_TOP[na])
     return _long() if name == "long" else _ladybug() if name == "ladybug" else _banded(na)
 
 
@@ -168,6 +176,8 @@ STAGE = [(name, na, kind, {}) for kind in ("huber", "cauchy")
                           ("long", 6))]
 STAGE += [("banded", 6, "huber", dict(pivot="first2")),
           ("banded", 6, "cauchy", dict(fix_structure=True))]
+# the _loss segment chunks of the other camera models
+STAGE += [("ladder", na, "huber", {}) for na in (7, 10, 12)]
 
 
 def _dense(sc, pt, cam, ox):
@@ -197,6 +207,9 @@ def test_weighted_linearisation_within_the_reference_bounds(gpu, oracle, poracle
         info = ba.step(relinearize=False, update_lm=False)
         plan = ba.plan_info()
     assert plan["ordered"] == 0 and (name != "long" or plan["long_points"] == 1), plan
+    if name == "ladder":    # the planted tracks of at least 91 views: segment chunks
+        import track_scenes as ts
+        assert plan["long_points"] == ts.is_long(np.bincount(pt)).sum() >= 10, plan
     X, vis = _dense(sc, pt, cam, ox)
     if na == 12:
         ref1 = poracle.mex1(a, b, X, vis)

@@ -248,24 +248,25 @@ def _environ(env):
 _RUNS = {}
 
 
-def _run(gpu, key):
+def _run(gpu, key, cases=None):
     """One context per case, shared by the stages' tests (nothing here is
     modified afterwards): the linearisation, the reduced system, the step at
-    the same linearisation, then an LM-applied step and its parameters."""
+    the same linearisation, then an LM-applied step and its parameters.
+    cases: another module's case table (keys of its own), default CASES."""
     if key in _RUNS:
         if isinstance(_RUNS[key], BaseException):    # never run a failed case again
             pytest.fail(f"{key}: the case's run failed in an earlier test: {_RUNS[key]!r}")
         return _RUNS[key]
     try:
-        _RUNS[key] = _run_case(gpu, key)
+        _RUNS[key] = _run_case(gpu, key, cases)
     except BaseException as exc:
         _RUNS[key] = exc
         raise
     return _RUNS[key]
 
 
-def _run_case(gpu, key):
-    c = CASES[key]
+def _run_case(gpu, key, cases=None):
+    c = (cases or CASES)[key]
     sc, pt, cam, ox = c["scene"]()
     na, kw = c["na"], dict(c["kw"])
     m, n = sc.m, sc.n
@@ -303,9 +304,9 @@ def _run_case(gpu, key):
     return r
 
 
-def _facts(r, key):
+def _facts(r, key, cases=None):
     """The plan facts that prove the intended kernels ran."""
-    c = CASES[key]
+    c = (cases or CASES)[key]
     assert c["plan"](r["plan"]), (key, r["plan"])
     for k, ok in c["launches"].items():
         assert ok(r["counts"][k]), (key, k, r["counts"])

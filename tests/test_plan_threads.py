@@ -42,12 +42,21 @@ def _hash(exe, path, threads):
     return re.search(r"hash ([0-9a-f]+)", r.stdout).group(1), r.stdout
 
 
-@pytest.mark.parametrize("name", ["cfg5x_300", "ladybug_small", "banded"])
+@pytest.mark.parametrize("name", ["cfg5x_300", "ladybug_small", "banded", "ladder6_257",
+                                  "ladder12_280", "shared_257"])
 def test_plan_identical_on_threads(harness, name):
     sys.path.insert(0, os.path.join(ROOT, "tools"))
     from bundleadjustmentmatlab_amd.scene import make_config
     exe, out = harness
-    if name == "cfg5x_300":      # short, per-term and long tracks (up to 76 views), re-detections
+    if name in ("ladder6_257", "ladder12_280", "shared_257"):
+        # tests/track_scenes.py: tracks on every length threshold up to three
+        # full segments; 257 long tracks through the same 90 cameras
+        import track_scenes as ts
+        sc, pt, cam, _ = {"ladder6_257": lambda: ts.ladder(6, 257),
+                          "ladder12_280": lambda: ts.ladder(12, 280),
+                          "shared_257": lambda: ts.shared(257)}[name]()
+        m, n = sc.m, sc.n
+    elif name == "cfg5x_300":    # short, per-term and long tracks (up to 76 views), re-detections
         from prof_cfg5x_solve import sub_problem
         sc = make_config("cfg5x")
         used, pt, cam, _ = sub_problem(sc, 300)

@@ -23,7 +23,27 @@ SCENES = {
     "cfg2-10": ("cfg2", dict(m=13, n=400, seed=3), 10),
     "ladybug": ("ladybug", dict(m=40, n=1500, max_track=30, radius=150.0, seed=23), 6),
     "cfg3-t10": ("cfg3", dict(m=40, n=2000, track=10, seed=6), 6),
+    # tests/track_scenes.py: 64 tracks of 91..100 views through the same 90
+    # cameras (blocks of 64 and more points: sums of several hundred terms), and
+    # two 257-view tracks (camera sums of 257 terms more) at num_a 6 and 10
+    "shared-64": ("shared", dict(C=64), 6),
+    "track-257": ("planted", dict(m=260, base_n=150, seed=5,
+                                  tracks=((2, 259, 1), (0, 257, 1))), 6),
+    "track-257-10": ("planted", dict(m=260, base_n=150, seed=5,
+                                     tracks=((2, 259, 1), (0, 257, 1))), 10),
 }
+
+
+def _scene(cfg, kw):
+    from bundleadjustmentmatlab_amd.scene import make_config
+    if cfg == "shared":
+        import track_scenes as ts
+        return ts.shared(**kw)[0]
+    if cfg == "planted":
+        import track_scenes as ts
+        kw = dict(kw, tracks=[np.arange(*t) for t in kw["tracks"]])
+        return ts.planted(**kw)[0]
+    return make_config(cfg, **kw)
 
 
 def start_params(sc, num_a):
@@ -46,9 +66,8 @@ def _case(name, lam=LAM):
     """One oracle pass of the scene at lam and the reference of its stages
     (computed once, shared, never modified: the tests copy what they change)."""
     import bundle_euclid_ref as oracle
-    from bundleadjustmentmatlab_amd.scene import make_config
     cfg, kw, na = SCENES[name]
-    sc = make_config(cfg, **kw)
+    sc = _scene(cfg, kw)
     a, b = start_params(sc, na)
     pb = oracle.SparseProblem(sc.m, sc.n, sc.obs_pt, sc.obs_cam, sc.obs_x, sc.K)
     L = oracle.sp_linearize(pb, a, b, na)
@@ -98,7 +117,7 @@ def _offdiag_block(c, smallest=False):
     return off[np.argmax(r["npts"][off])]
 
 
-@pytest.mark.parametrize("name", ["cfg2-6", "cfg2-10", "ladybug"])
+@pytest.mark.parametrize("name", ["cfg2-6", "cfg2-10", "ladybug", "shared-64", "track-257"])
 def test_bound_has_teeth_on_s(oracle, name):
     c = _case(name)
     na, sc, r = c["na"], c["sc"], c["ref"]
@@ -158,6 +177,30 @@ def test_bound_has_teeth_on_db(oracle):
     bad = db[6].copy()
     bad[np.unravel_index(np.argmax(np.abs(bad)), bad.shape)] *= 1 + 1e-10
     assert sr.db_ratio(bad, ref, bnd) > 1.0
+
+
+@pytest.mark.parametrize("name", ["track-257", "track-257-10"])
+def test_bound_has_teeth_on_a_long_tracks_last_view(oracle, name):
+    """A 257-view track's db without the term of its 257th observation (what a
+    256-lane loop that forgot its second trip would give) leaves the bound,
+    with ndb = 6 and ndb = num_a alike."""
+    c = _case(name)
+    na, sc = c["na"], c["sc"]
+    pt, cam = sc.obs_pt, sc.obs_cam
+    da = oracle.chol_solve_fixed(c["S"], c["e"])
+    W = w_of(c["L"]["W"], na)
+    i = sc.base_n
+    last = np.flatnonzero(pt == i)[-1]
+    assert (pt == i).sum() == 257
+    for ndb in sorted({6, na}):
+        db = oracle.sp_update(c["pb"], c["L"]["W"], da, c["L"]["eB"], c["Vi"], c["a"], c["b"],
+                              na, ndb=ndb)[0]
+        ref, bnd = sr.back_subst(na, ndb, pt, cam, W, c["Vi"], c["L"]["eB"], da)
+        assert sr.db_ratio(db, ref, bnd) <= 1.0
+        term = W[:ndb, :, last].T @ da.reshape(na, -1, order="F")[:ndb, cam[last]]
+        bad = db.copy()
+        bad[:, i] += c["Vi"][:, :, i] @ term
+        assert sr.db_ratio(bad, ref, bnd) > 1.0, ndb
 
 
 @pytest.mark.parametrize("name", ["cfg2-6", "cfg2-10", "ladybug", "cfg3-t10"])
