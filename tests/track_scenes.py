@@ -29,7 +29,7 @@ CH_OBS, CH_TERMS = 128, 4096           # BA_CH_OBS, BA_CH_TERMS
 
 
 def is_long(k):
-    """track_kind(k) == 2 (ba_solver.cpp): more than a per-term chunk holds."""
+    """track_kind(k) == 2 (ba_plan.cpp): more than a per-term chunk holds."""
     k = np.asarray(k, dtype=np.int64)
     return (k > CH_OBS) | (k * (k + 1) // 2 > CH_TERMS)
 

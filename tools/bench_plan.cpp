@@ -1,17 +1,21 @@
-// Host-side setup of a context, timed on the CPU (no GPU needed): the
-// observation sort, the track-kind point order and plan_host (co-visible block
-// set + chunk / group plan) of ba_solver.cpp, on a problem read from a file.
-// Prints the phase times and an FNV-1a hash of every plan vector, so that a
-// reimplementation of the planner can be checked to produce the same plan.
+// Host-side setup of a context, timed on the CPU (no GPU and no ROCm needed):
+// the observation sort, the track-kind point order and plan_host (co-visible
+// block set + chunk / group plan) of csrc/ba_plan.cpp, on a problem read from
+// a file.  Prints the phase times and an FNV-1a hash of every plan vector, so
+// that a change of the planner can be checked to produce the same plan
+// (tests/test_plan_threads.py pins the hashes, tests/test_plan_sanitize.py runs
+// this program under the sanitizers).
 //
-// Build (tools/bench_plan.sh): hipcc -O3 -std=c++17 -I include
-//   tools/bench_plan.cpp <the library's kernel objects> -lrccl -o tools/build/bench_plan
+// Build (tools/bench_plan.sh), with any C++17 compiler:
+//   c++ -O3 -std=c++17 -I include -pthread tools/bench_plan.cpp
+//       bundleadjustmentmatlab_amd/csrc/ba_plan.cpp -o tools/build/bench_plan
 // Input: int32 m, n, N, then int32 obs_pt[N], int32 obs_cam[N].
-#include "../bundleadjustmentmatlab_amd/csrc/ba_solver.cpp"
-#include "../bundleadjustmentmatlab_amd/csrc/ba_cov.hip"   // ba_solver.cpp's covariance launchers
+#include "../bundleadjustmentmatlab_amd/csrc/ba_plan.h"
 
 #include <chrono>
 #include <cstdio>
+#include <cstdlib>
+#include <vector>
 
 namespace {
 struct fnv {
@@ -111,7 +115,7 @@ int main(int argc, char **argv)
                                        P.nseg, P.max_blob, P.mf_max_blob, (int)P.n_terms,
                                        fast ? 1 : 0, p_long};
         H.add(scal);
-        {   // MFMA chunk records: camera count and flush flag (ba_solver.cpp build_plan)
+        {   // MFMA chunk records: camera count and flush flag (ba_plan.cpp build_plan)
             int flush = 0, dense = 0;
             long long csum = 0;
             for (int c = 0; c < P.nch_mf; c++) {

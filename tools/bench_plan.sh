@@ -1,15 +1,13 @@
 #!/bin/bash
-# Build tools/build/bench_plan (the CPU harness of the context's host planner,
-# tools/bench_plan.cpp) against the library's kernel objects, and write the
-# problem files it reads (tools/build/plan_*.bin).
+# Build tools/build/bench_plan (the CPU harness of the context's host planner:
+# tools/bench_plan.cpp + csrc/ba_plan.cpp, host compiler only, with the
+# planner's phase times on stderr), and write the problem files it reads
+# (tools/build/plan_*.bin).
 set -e
 cd "$(dirname "$0")/.."
-make -s -C bundleadjustmentmatlab_amd/csrc -j8
 mkdir -p tools/build
-O=bundleadjustmentmatlab_amd/csrc/build
-/opt/rocm/bin/hipcc -O3 -std=c++17 -fPIC --offload-arch=gfx950 -ffp-contract=off -DBA_PLAN_TIMING -I include \
-  -x hip tools/bench_plan.cpp -x none $O/ba_kernels.hip.o $O/ba_chol.hip.o $O/ba_resect.hip.o \
-  $O/ba_scene.hip.o -L/opt/rocm/lib -lrccl -Wl,-rpath,/opt/rocm/lib -o tools/build/bench_plan
+${CXX:-c++} -O3 -std=c++17 -ffp-contract=off -DBA_PLAN_TIMING -I include -pthread \
+  tools/bench_plan.cpp bundleadjustmentmatlab_amd/csrc/ba_plan.cpp -o tools/build/bench_plan
 python3 - <<'PY'
 import sys
 import numpy as np
