@@ -25,7 +25,7 @@
 // then the backward solve x_k = L_kk^-T z_k, z_j -= L_kj^T x_k (one launch,
 // k_backward_all, or per column k_backward).
 //
-// Solvers on top of the tiles (ba_chol_setup picks one): block cyclic
+// Solvers on top of the tiles (chol_plan_build, ba_chol_plan.cpp, picks one): block cyclic
 // reduction when S is tile-tridiagonal (k_cr32_fused on camera-aligned 30-row
 // tiles); else the envelope Cholesky, on a nested-dissection camera order
 // (arcs side by side in k_factor_multi, separator SYRK k_sep_update /
@@ -33,6 +33,7 @@
 // the sequential k_chol_seq in parity mode.
 #include "ba_internal.h"
 #include "ba_camera.h"
+#include "ba_chol_plan.h"
 
 #include <algorithm>
 #include <atomic>
@@ -44,6 +45,7 @@
 #include <vector>
 
 #define NB 64
+static_assert(NB == BA_TILE, "the kernels' tile height is the planner's");
 #define LP 66  // LDS row pitch (doubles): conflict-free 16x4 MFMA operand reads
 
 typedef double d4 __attribute__((ext_vector_type(4)));
@@ -998,22 +1000,7 @@ __global__ __launch_bounds__(256) void k_factor_step(double *__restrict__ S, lon
 
 // one step of every arc of the nested dissection: column k[t] of arc t takes
 // workgroups [b0[t], b0[t+1]) (k_factor_step's roles), pan / prev as offsets
-// into the panel list
-// Workgroup order (grouped, the default): every arc's workgroup 0 first, then
-// every arc's panel tiles, then every arc's trailing pairs (pb / tb: prefix
-// counts of the panels / trailing pairs over the arcs).  Arc-major order
-// (b0, VLGBA_ND_GROUPED=0) puts arc 1's workgroup 0 behind all of arc 0's
-// trailing pairs: once those outnumber the free workgroup slots, arc 1's
-// diagonal factor -- the chain of its step -- starts only when the first of
-// them retire.  The roles are the same either way (bit-identical).
-struct nd_step {
-    int np, grouped;
-    int k[BA_ND_MAX], T[BA_ND_MAX], Tp[BA_ND_MAX], pofs[BA_ND_MAX], qofs[BA_ND_MAX];
-    int ntr[BA_ND_MAX], ts[BA_ND_MAX];   // trailing pairs / their workgroups (stride)
-    int kend[BA_ND_MAX];                 // runner mode: arc t's end column (else 0)
-    int b0[BA_ND_MAX + 1], pb[BA_ND_MAX + 1], tb[BA_ND_MAX + 1];
-};
-
+// into the panel list (nd_step, ba_chol_plan.h: grouped by role, or arc-major)
 __global__ __launch_bounds__(256) void k_factor_multi(double *__restrict__ S, long long lds,
                                                       const int *__restrict__ pan_list,
                                                       nd_step P, int sep0,
@@ -1066,11 +1053,7 @@ __global__ __launch_bounds__(256) void k_factor_multi(double *__restrict__ S, lo
 //   that gives up sets status[1] and ends the workgroup (the host re-solves
 //   without hand-offs).
 // ---------------------------------------------------------------------------
-struct env_runs {
-    int np;
-    int k0[BA_ND_MAX], k1[BA_ND_MAX];
-};
-
+// (the runs: env_runs, ba_chol_plan.h)
 __global__ __launch_bounds__(256) void k_env_runner(double *S, long long lds,
                                                     const int *__restrict__ pan_ptr,
                                                     const int *__restrict__ pan_list, env_runs Rn,
@@ -1644,6 +1627,7 @@ __global__ __launch_bounds__(256) void k_cr_update(double *__restrict__ S, long 
 // 32 columns instead of 64.
 // ---------------------------------------------------------------------------
 #define T32 32
+static_assert(T32 == BA_TILE32, "the camera-aligned CR's tile height is the planner's");
 
 // In-launch hand-offs of the one-launch cyclic reduction (k_cr32_fused):
 // every byte one workgroup hands to another is stored write-through (sc1,
@@ -2584,18 +2568,10 @@ __global__ __launch_bounds__(256) void k_cr32_back_all(const int *__restrict__ e
 // spin is bounded (timeout word status[1]: the host re-solves with the per-level
 // launches).
 // ---------------------------------------------------------------------------
-#define BA_CR_MAXLEV 30
 #ifndef BA_CR_PW
 #define BA_CR_PW 1
 #endif
-struct cr32_fplan {
-    int nl, nrec;
-    int l0two;                     // level 0 in 2 records per tile (roles 4 | 2), else 3
-    int b0[BA_CR_MAXLEV + 2];      // first block of level L; b0[nl] = first back block
-    int fofs[BA_CR_MAXLEV + 1];    // level L >= 1: first fused record in crf
-    int sofs[BA_CR_MAXLEV + 1];    //               first survivor record in crs
-    int eofs[BA_CR_MAXLEV + 2];    // elimination records of level L in cr_elim
-};
+// (the block ranges: cr32_fplan, ba_chol_plan.h)
 
 __device__ __forceinline__ void cr32_wait_flags(const unsigned *flag, int nw, const int w[8],
                                                 unsigned epoch, double *status)
@@ -3059,573 +3035,157 @@ static int dev_alloc(T **p, size_t bytes)
     return *p ? 0 : -(int)hipErrorOutOfMemory;
 }
 
-// ---- nested dissection of the envelope (host planner) -------------------
-namespace {
-struct nd_cost_t {
-    int crit, ns, n[BA_ND_MAX];
-};
-
-// arcs [bnd[t], bnd[t+1]) of consecutive cameras; camera j of arc t joins the
-// separator when it is co-visible with a camera of an earlier arc (minK[j] <
-// bnd[t]).  Predicted step chain: the longest arc, the separator's columns,
-// and the two SYRK launches between them.
-nd_cost_t nd_cost(const std::vector<int> &minK, int na, const int *bnd, int K)
+// ---- the solve's setup: plan on the host (ba_chol_plan.cpp), allocate, upload
+static bool env_is(const char *name, char c)
 {
-    nd_cost_t e{};
-    int nsep = 0, mx = 0;
-    for (int t = 0; t < K; t++) {
-        int cnt = 0;
-        for (int j = bnd[t]; j < bnd[t + 1]; j++) {
-            if (minK[j] < bnd[t])
-                nsep++;
-            else
-                cnt++;
-        }
-        e.n[t] = (na * cnt + NB - 1) / NB;
-        mx = std::max(mx, e.n[t]);
-    }
-    e.ns = (na * nsep + NB - 1) / NB;
-    e.crit = mx + e.ns + (e.ns > 0 ? 2 : 0);
-    return e;
-}
-
-// K = 2 .. BA_ND_MAX arcs: equal camera counts, then one boundary at a time
-// moved while the predicted chain shortens.  Returns the best K (0: none).
-int nd_choose(const std::vector<int> &minK, int m, int na, int *bnd_out, int &crit_out)
-{
-    int bestK = 0;
-    crit_out = INT_MAX;
-    for (int K = 2; K <= BA_ND_MAX && K <= m; K++) {
-        int bnd[BA_ND_MAX + 1];
-        for (int t = 0; t <= K; t++) bnd[t] = (int)((long long)t * m / K);
-        nd_cost_t cur = nd_cost(minK, na, bnd, K);
-        for (int sweep = 0; sweep < 4; sweep++) {
-            bool moved = false;
-            for (int t = 1; t < K; t++)
-                for (int step = std::max(1, m / (4 * K)); step >= 1; step /= 2)
-                    for (int dir = -1; dir <= 1; dir += 2)
-                        for (;;) {
-                            const int nbd = bnd[t] + dir * step;
-                            if (nbd <= bnd[t - 1] || nbd >= bnd[t + 1]) break;
-                            const int keep = bnd[t];
-                            bnd[t] = nbd;
-                            const nd_cost_t c = nd_cost(minK, na, bnd, K);
-                            if (c.crit < cur.crit) {
-                                cur = c;
-                                moved = true;
-                            } else {
-                                bnd[t] = keep;
-                                break;
-                            }
-                        }
-            if (!moved) break;
-        }
-        if (cur.crit < crit_out) {
-            crit_out = cur.crit;
-            bestK = K;
-            for (int t = 0; t <= K; t++) bnd_out[t] = bnd[t];
-        }
-    }
-    return bestK;
-}
-}   // namespace
-
-static std::vector<int> nd_min_cam(int m, const int *blk_jk, int nb)
-{
-    std::vector<int> minK(m);
-    for (int j = 0; j < m; j++) minK[j] = j;
-    for (int b = 0; b < nb; b++) {
-        const int j = blk_jk[2 * b], k = blk_jk[2 * b + 1];
-        if (k < minK[j]) minK[j] = k;
-    }
-    return minK;
-}
-
-extern "C" int vlgba_debug_nd_plan(int m, int num_a, const int *blk_jk, int nb, int *bnd,
-                                   int *crit)
-{
-    if (m < 2 || num_a < 1 || nb < 0 || (nb > 0 && !blk_jk) || !bnd || !crit) return -1;
-    for (int b = 0; b < nb; b++)
-        if (blk_jk[2 * b] < blk_jk[2 * b + 1] || blk_jk[2 * b + 1] < 0 || blk_jk[2 * b] >= m)
-            return -1;
-    return nd_choose(nd_min_cam(m, blk_jk, nb), m, num_a, bnd, *crit);
+    const char *e = std::getenv(name);
+    return e && e[0] == c;
 }
 
 int ba_chol_setup(ba_dev *d, const int *blk_jk, int nb)
 {
-    int nt = (int)(d->lds / NB);
-    d->nt = nt;
-    d->h_tfirst = new int[nt];
-    d->fl_factor = d->fl_syrk = d->fl_back = 0.0;
-    // every lower tile for the measurement mode (1) and the sequential parity
-    // solve (3); the envelope otherwise (0 auto, 2 envelope without CR, 4 ND)
-    const bool all_tiles = d->dense_solve == 1 || d->dense_solve == 3;
-    for (int i = 0; i < nt; i++) d->h_tfirst[i] = all_tiles ? 0 : i;
-    if (!all_tiles)
-        for (int b = 0; b < nb; b++) {
-            const int j = blk_jk[2 * b], k = blk_jk[2 * b + 1];   // j >= k
-            const long long r0 = (long long)d->na * j, c0 = (long long)d->na * k;
-            for (long long r = r0; r < r0 + d->na; r++) {
-                const int ti = (int)(r / NB);
-                const int tk = (int)(c0 / NB);
-                if (tk < d->h_tfirst[ti]) d->h_tfirst[ti] = tk;
-            }
-        }
-    // cyclic reduction when S is tile-tridiagonal (dense_solve 0 = auto):
-    // camera-aligned 32-row tiles when the co-visibility band allows them
-    // (every block (j, k) within neighbouring groups of floor(32 / NA)
-    // cameras), else the 64-row tiles
-    d->cr_nlev = 0;
-    d->cr32 = 0;
-    int ntc = nt;
-    if (d->dense_solve == 0 && d->na <= 32) {
-        const int G = 32 / d->na, TB = d->na * G;
-        const int nt32 = (int)((d->ld + TB - 1) / TB);
-        bool ok = nt32 > 1;
-        for (int b = 0; ok && b < nb; b++) {
-            const int dj = blk_jk[2 * b] / G - blk_jk[2 * b + 1] / G;
-            if (dj > 1 || dj < -1) ok = false;
-        }
-        if (ok) {
-            d->cr32 = 1;
-            d->tb32 = TB;
-            d->nt32 = nt32;
-            ntc = nt32;
-            // direct assembly: every camera pair (j >= k) inside a group of G
-            // cameras is a block (the diagonal tiles the CR writes back are then
-            // fully rewritten by k_schur_reduce every pass)
-            long long inside = 0, want = 0;
-            for (int b = 0; b < nb; b++)
-                inside += blk_jk[2 * b] / G == blk_jk[2 * b + 1] / G;
-            for (int g0 = 0; g0 < d->m; g0 += G) {
-                const long long c = std::min(G, d->m - g0);
-                want += c * (c + 1) / 2;
-            }
-            d->asm_direct_ok = inside == want;
-        }
-    }
-    bool tridiag = d->dense_solve == 0 && nt > 1;
-    for (int i = 1; tridiag && i < nt; i++)
-        if (d->h_tfirst[i] < i - 1) tridiag = false;
-    if (d->cr32) tridiag = true;
-    if (tridiag) {
-        const int nt = ntc;   // the CR tile count (64- or camera-aligned 32-row tiles)
-        std::vector<int> act(nt), elim, keep, eptr{0}, kptr{0};
-        for (int i = 0; i < nt; i++) act[i] = i;
-        while (!act.empty()) {
-            const int len = (int)act.size();
-            std::vector<int> next;
-            for (int t = 0; t < len; t++) {
-                if ((t & 1) == 0) {
-                    elim.push_back(act[t]);
-                    elim.push_back(t > 0 ? act[t - 1] : -1);
-                    elim.push_back(t + 1 < len ? act[t + 1] : -1);
-                } else {
-                    keep.push_back(act[t]);
-                    keep.push_back(act[t - 1]);
-                    keep.push_back(t + 1 < len ? act[t + 1] : -1);
-                    keep.push_back(t + 2 < len ? act[t + 2] : -1);
-                    next.push_back(act[t]);
-                }
-            }
-            eptr.push_back((int)elim.size() / 3);
-            kptr.push_back((int)keep.size() / 4);
-            act.swap(next);
-        }
-        d->cr_nlev = (int)eptr.size() - 1;
-        {   // the CR's algorithmic flops (ba_dev::fl_factor): per elimination
-            // record (e, p, q) the factor + inverse of D_e, y_e and one panel per
-            // neighbour; per kept record (k, e-, e+, k2) the update of D_k and r_k
-            // by its eliminated neighbours and the fill towards k2; the back
-            // substitution's GEMVs
-            const double t = d->cr32 ? T32 : NB;
-            const double potri = 2.0 * t * t * t / 3.0, gemm = 2.0 * t * t * t, gemv = 2.0 * t * t;
-            d->fl_factor = d->fl_syrk = d->fl_back = 0.0;
-            for (size_t i = 0; i < elim.size(); i += 3) {
-                const double nbr = (elim[i + 1] >= 0) + (elim[i + 2] >= 0);
-                d->fl_factor += potri + gemv + nbr * gemm;
-                d->fl_back += (nbr + 1) * gemv;
-            }
-            for (size_t i = 0; i < keep.size(); i += 4) {
-                const double nbe = 1 + (keep[i + 2] >= 0);
-                d->fl_factor += nbe * (gemm + gemv) + (keep[i + 3] >= 0) * gemm;
-            }
-        }
-        if (d->cr32) {   // the fused levels' records (see k_cr32_level)
-            const int nl = d->cr_nlev;
-            std::vector<int> frec, srec, fptr(nl + 1, 0), sptr(nl + 1, 0);
-            std::vector<int> em_of(nt, -1), ep_of(nt, -1);
-            for (int L = 1; L < nl; L++) {
-                for (int i = kptr[L - 1]; i < kptr[L]; i++) {
-                    em_of[keep[4 * i]] = keep[4 * i + 1];
-                    ep_of[keep[4 * i]] = keep[4 * i + 2];
-                }
-                for (int i = eptr[L]; i < eptr[L + 1]; i++) {
-                    const int e = elim[3 * i];
-                    frec.insert(frec.end(), {e, elim[3 * i + 1], elim[3 * i + 2], em_of[e],
-                                             ep_of[e]});
-                }
-                for (int i = kptr[L]; i < kptr[L + 1]; i++) {
-                    const int k = keep[4 * i];
-                    srec.insert(srec.end(), {k, em_of[k], ep_of[k]});
-                }
-                fptr[L + 1] = (int)frec.size() / 5;
-                sptr[L + 1] = (int)srec.size() / 3;
-            }
-            fptr[1] = 0;
-            sptr[1] = 0;
-            d->crf_ptr_h = new int[nl + 1];
-            d->crs_ptr_h = new int[nl + 1];
-            for (int L = 0; L <= nl; L++) {
-                d->crf_ptr_h[L] = L >= 1 ? fptr[L] : 0;
-                d->crs_ptr_h[L] = L >= 1 ? sptr[L] : 0;
-            }
-            TRY_RC(dev_alloc(&d->xgran, sizeof(unsigned long long) * 64 * (size_t)nt));
-            VLGBA_CHECK(hipMemsetAsync(d->xgran, 0, sizeof(unsigned long long) * 64 * (size_t)nt,
+    const chol_plan_opts opt = {!env_is("VLGBA_CR_FUSED", '0'), env_is("VLGBA_ND", '0'),
+                                env_is("VLGBA_ND", 'v'), !env_is("VLGBA_ND_GROUPED", '0'),
+                                env_is("VLGBA_ENV_RUNNER", '1')};
+    const chol_plan_in in = {d->m, d->na, d->ld, d->lds, d->ncu, d->dense_solve, blk_jk, nb, opt};
+    d->plan = new chol_plan;
+    const chol_plan &P = *d->plan;
+    TRY_RC(chol_plan_build(in, *d->plan));
+    // the scalars the other files read
+    d->nt = P.nt;
+    d->n_env = P.n_env();
+    d->cr_nlev = P.cr_nlev;
+    d->cr32 = P.cr32;
+    d->tb32 = P.tb32;
+    d->nt32 = P.nt32;
+    d->asm_direct_ok = P.asm_direct_ok;
+    d->cr_fused = P.cr_fused;
+    d->nd_np = P.nd_np;
+    d->nd_grouped = P.nd_grouped;
+    for (int t = 0; t <= BA_ND_MAX; t++) d->nd_a0[t] = P.nd_a0[t];
+    if (P.nd_np > 0) d->slds = P.slds;
+    d->nd_npair = P.nd_npair;
+    d->nd_nrec = P.nd_nrec;
+    d->fl_factor = P.fl_factor;
+    d->fl_syrk = P.fl_syrk;
+    d->fl_back = P.fl_back;
+    d->env_runner = P.env_runner;
+
+    const int nt = P.nt;
+    auto put = [&](int *dst, const std::vector<int> &v) -> int {   // (nothing when empty)
+        if (!v.empty())
+            VLGBA_CHECK(hipMemcpyAsync(dst, v.data(), sizeof(int) * v.size(),
+                                       hipMemcpyHostToDevice, d->stream));
+        return 0;
+    };
+    if (P.cr_nlev > 0) {   // cyclic reduction: its records, L(p, e) | L(q, e)
+        const int ntc = P.cr_tiles();
+        if (P.cr32) {
+            TRY_RC(dev_alloc(&d->xgran, sizeof(unsigned long long) * 64 * (size_t)ntc));
+            VLGBA_CHECK(hipMemsetAsync(d->xgran, 0, sizeof(unsigned long long) * 64 * (size_t)ntc,
                                        d->stream));
             d->back_epoch = 0;
-            {   // one-launch CR (k_cr32_fused) unless VLGBA_CR_FUSED=0
-                const char *ev = std::getenv("VLGBA_CR_FUSED");
-                d->cr_fused = !(ev && ev[0] == '0') && nl <= BA_CR_MAXLEV;
-            }
-            if (d->cr_fused) {
-                const size_t nfl = (size_t)5 * nl * nt;
+            if (P.cr_fused) {
+                const size_t nfl = (size_t)5 * P.cr_nlev * ntc;
                 TRY_RC(dev_alloc(&d->crflag, sizeof(unsigned) * nfl));
                 VLGBA_CHECK(hipMemsetAsync(d->crflag, 0, sizeof(unsigned) * nfl, d->stream));
             }
-            TRY_RC(dev_alloc(&d->crf, sizeof(int) * (frec.size() + 1)));
-            TRY_RC(dev_alloc(&d->crs, sizeof(int) * (srec.size() + 1)));
-            if (!frec.empty())
-                VLGBA_CHECK(hipMemcpyAsync(d->crf, frec.data(), sizeof(int) * frec.size(),
-                                           hipMemcpyHostToDevice, d->stream));
-            if (!srec.empty())
-                VLGBA_CHECK(hipMemcpyAsync(d->crs, srec.data(), sizeof(int) * srec.size(),
-                                           hipMemcpyHostToDevice, d->stream));
+            TRY_RC(dev_alloc(&d->crf, sizeof(int) * (P.frec.size() + 1)));
+            TRY_RC(dev_alloc(&d->crs, sizeof(int) * (P.srec.size() + 1)));
+            TRY_RC(put(d->crf, P.frec));
+            TRY_RC(put(d->crs, P.srec));
             VLGBA_CHECK(hipStreamSynchronize(d->stream));
         }
-        d->cr_eptr_h = new int[eptr.size()];
-        d->cr_kptr_h = new int[kptr.size()];
-        for (size_t q = 0; q < eptr.size(); q++) d->cr_eptr_h[q] = eptr[q];
-        for (size_t q = 0; q < kptr.size(); q++) d->cr_kptr_h[q] = kptr[q];
-        TRY_RC(dev_alloc(&d->cr_elim, sizeof(int) * elim.size()));
-        TRY_RC(dev_alloc(&d->cr_keep, sizeof(int) * (keep.size() + 1)));
-        TRY_RC(dev_alloc(&d->crL, sizeof(double) * 2 * (size_t)nt *
-                                      (d->cr32 ? T32 * T32 : NB * NB)));
-        VLGBA_CHECK(hipMemcpyAsync(d->cr_elim, elim.data(), sizeof(int) * elim.size(),
-                                   hipMemcpyHostToDevice, d->stream));
-        if (!keep.empty())
-            VLGBA_CHECK(hipMemcpyAsync(d->cr_keep, keep.data(), sizeof(int) * keep.size(),
-                                       hipMemcpyHostToDevice, d->stream));
+        TRY_RC(dev_alloc(&d->cr_elim, sizeof(int) * P.elim.size()));
+        TRY_RC(dev_alloc(&d->cr_keep, sizeof(int) * (P.keep.size() + 1)));
+        TRY_RC(dev_alloc(&d->crL, sizeof(double) * 2 * (size_t)ntc *
+                                      (P.cr32 ? T32 * T32 : NB * NB)));
+        TRY_RC(put(d->cr_elim, P.elim));
+        TRY_RC(put(d->cr_keep, P.keep));
     }
-    // nested dissection (not for tridiagonal S, which the cyclic reduction takes)
-    d->nd_np = 0;
-    {
-        const char *eg = std::getenv("VLGBA_ND_GROUPED");
-        d->nd_grouped = !(eg && eg[0] == '0');
-    }
-    const int na = d->na, m = d->m;
-    std::vector<int> crow, tpart;   // row of camera j; part of tile (arc t, separator np)
-    if (!tridiag && (d->dense_solve == 0 || d->dense_solve == 4) && m >= 2 && nt > 1) {
-        const char *ev = std::getenv("VLGBA_ND");
-        const bool off = ev && ev[0] == '0';
-        const std::vector<int> minK = nd_min_cam(m, blk_jk, nb);
-        int bnd[BA_ND_MAX + 1], crit = INT_MAX;
-        const int K = off && d->dense_solve == 0 ? 0 : nd_choose(minK, m, na, bnd, crit);
-        bool take = K > 0 && (d->dense_solve == 4 || (nt >= 8 && 4 * crit <= 3 * nt));
-        // setup budget: the separator SYRK's host lists cost
-        // O(ns^2 s0) and its partials (pairs + CUs) x 33 KB of device memory --
-        // a graph with a wide separator keeps the natural order instead
-        long long npair_max = 0, setup_ops = 0;
-        if (K > 0) {
-            const nd_cost_t c = nd_cost(minK, na, bnd, K);
-            long long s0t = 0;
-            for (int t = 0; t < K; t++) s0t += c.n[t];
-            npair_max = (long long)c.ns * (c.ns + 1) / 2;
-            setup_ops = npair_max * s0t;
-            if (npair_max > BA_ND_MAX_PAIRS || setup_ops > BA_ND_MAX_SETUP) take = false;
-        }
-        if (ev && ev[0] == 'v')
-            std::fprintf(stderr, "[vlgba] nested dissection: natural %d tiles, %d arcs -> chain %d, "
-                         "<= %lld separator pairs, %lld setup checks%s\n", nt, K, crit, npair_max,
-                         setup_ops, take ? "" : " (not taken)");
-        if (take) {
-            crow.assign(m, -1);
-            long long row = 0;
-            for (int t = 0; t < K; t++) {
-                d->nd_a0[t] = (int)(row / NB);
-                for (int j = bnd[t]; j < bnd[t + 1]; j++)
-                    if (minK[j] >= bnd[t]) {
-                        crow[j] = (int)row;
-                        row += na;
-                    }
-                row = (row + NB - 1) / NB * NB;
-            }
-            d->nd_a0[K] = (int)(row / NB);
-            for (int t = 0; t < K; t++)
-                for (int j = bnd[t]; j < bnd[t + 1]; j++)
-                    if (minK[j] < bnd[t]) {
-                        crow[j] = (int)row;
-                        row += na;
-                    }
-            row = (row + NB - 1) / NB * NB;
-            d->nd_np = K;
-            d->slds = row;
-            nt = (int)(row / NB);
-            d->nt = nt;
-            tpart.assign(nt, K);
-            for (int t = 0; t < K; t++)
-                for (int i = d->nd_a0[t]; i < d->nd_a0[t + 1]; i++) tpart[i] = t;
-        }
-    }
-    const bool nd = d->nd_np > 0;
-    const int npart = nd ? d->nd_np + 1 : 1;
-    const int s0 = nd ? d->nd_a0[d->nd_np] : nt;
-    // first[i][P]: the first envelope tile of row i among the columns of part P
-    // (the profile is preserved inside each part: arcs never couple, and the
-    // separator block fills in, so it is taken dense)
-    std::vector<int> first;
-    if (nd) {
-        delete[] d->h_tfirst;
-        d->h_tfirst = new int[nt];
-        first.assign((size_t)nt * npart, INT_MAX);
-        for (int i = 0; i < nt; i++) first[(size_t)i * npart + tpart[i]] = i >= s0 ? s0 : i;
-        for (int b = 0; b < nb; b++) {
-            long long r0 = crow[blk_jk[2 * b]], c0 = crow[blk_jk[2 * b + 1]];
-            if (r0 < c0) std::swap(r0, c0);
-            const int tk = (int)(c0 / NB), P = tpart[tk];
-            for (long long r = r0; r < r0 + na; r++) {
-                int &f = first[(size_t)(r / NB) * npart + P];
-                if (tk < f) f = tk;
-            }
-        }
-        for (int i = 0; i < nt; i++) {
-            int f = i;
-            for (int P = 0; P < npart; P++) f = std::min(f, first[(size_t)i * npart + P]);
-            d->h_tfirst[i] = f;
-        }
-    } else {
-        first.assign(d->h_tfirst, d->h_tfirst + nt);
-    }
-    auto in_env = [&](int i, int k) { return first[(size_t)i * npart + (nd ? tpart[k] : 0)] <= k; };
-    std::vector<int> ptr(nt + 1, 0), list, env;
-    for (int k = 0; k < nt; k++) {
-        for (int i = k + 1; i < nt; i++)
-            if (in_env(i, k)) list.push_back(i);
-        ptr[k + 1] = (int)list.size();
-    }
-    for (int k = 0; k < nt; k++)
-        for (int i = k; i < nt; i++)
-            if (in_env(i, k)) {
-                env.push_back(i);
-                env.push_back(k);
-            }
-    d->n_env = (int)env.size() / 2;
-    {   // per envelope tile: the co-visible blocks (j >= k) overlapping it
-        std::vector<int> tid_of((size_t)nt * nt, -1);
-        for (int e = 0; e < d->n_env; e++) tid_of[(size_t)env[2 * e] * nt + env[2 * e + 1]] = e;
-        std::vector<std::vector<int>> lists(d->n_env);
-        for (int b = 0; b < nb; b++) {
-            long long r0 = (long long)na * blk_jk[2 * b], c0 = (long long)na * blk_jk[2 * b + 1];
-            if (nd) {
-                r0 = crow[blk_jk[2 * b]];
-                c0 = crow[blk_jk[2 * b + 1]];
-                if (r0 < c0) std::swap(r0, c0);
-            }
-            const int t0 = (int)(r0 / NB), t1 = (int)((r0 + na - 1) / NB);
-            const int u0 = (int)(c0 / NB), u1 = (int)((c0 + na - 1) / NB);
-            for (int t = t0; t <= t1; t++)
-                for (int u = u0; u <= u1 && u <= t; u++) {
-                    const int e = tid_of[(size_t)t * nt + u];
-                    if (e >= 0) lists[e].push_back(b);
-                }
-        }
-        std::vector<int> tptr(d->n_env + 1, 0), tblk;
-        for (int e = 0; e < d->n_env; e++) {
-            tblk.insert(tblk.end(), lists[e].begin(), lists[e].end());
-            tptr[e + 1] = (int)tblk.size();
-        }
-        TRY_RC(dev_alloc(&d->tb_ptr, sizeof(int) * tptr.size()));
-        TRY_RC(dev_alloc(&d->tb_blk, sizeof(int) * (tblk.size() + 1)));
-        VLGBA_CHECK(hipMemcpyAsync(d->tb_ptr, tptr.data(), sizeof(int) * tptr.size(),
-                                   hipMemcpyHostToDevice, d->stream));
-        if (!tblk.empty())
-            VLGBA_CHECK(hipMemcpyAsync(d->tb_blk, tblk.data(), sizeof(int) * tblk.size(),
-                                       hipMemcpyHostToDevice, d->stream));
-        VLGBA_CHECK(hipStreamSynchronize(d->stream));
-    }
+    // per envelope tile: the co-visible blocks (j >= k) overlapping it
+    TRY_RC(dev_alloc(&d->tb_ptr, sizeof(int) * P.tptr.size()));
+    TRY_RC(dev_alloc(&d->tb_blk, sizeof(int) * (P.tblk.size() + 1)));
+    TRY_RC(put(d->tb_ptr, P.tptr));
+    TRY_RC(put(d->tb_blk, P.tblk));
+    VLGBA_CHECK(hipStreamSynchronize(d->stream));
     // the factor's storage: S (dense, column major), the diagonal tiles'
     // inverses, the forward-solve result (+ the 32-row CR's last tile)
-    const long long sdim = nd ? d->slds : d->lds;
+    const bool nd = P.nd_np > 0;
+    const long long sdim = nd ? P.slds : d->lds;
     TRY_RC(dev_alloc(&d->S, sizeof(double) * (size_t)(sdim * sdim)));
     TRY_RC(dev_alloc(&d->linv, sizeof(double) * (size_t)(sdim / NB) * NB * NB));
     TRY_RC(dev_alloc(&d->ywork, sizeof(double) * (size_t)(sdim + NB)));
     if (nd) {
-        std::vector<int> rowsrc(d->slds, -1), prow(d->lds, -1);
-        for (int j = 0; j < m; j++)
-            for (int r = 0; r < na; r++) {
-                rowsrc[crow[j] + r] = na * j + r;
-                prow[(size_t)na * j + r] = crow[j] + r;
-            }
-        // separator pairs (i >= j, ascending) and their arc columns, chunked
-        std::vector<int> pairs, pptr{0}, rec, klist;
-        std::vector<std::vector<int>> kl;
-        long long work = 0;
-        for (int i = s0; i < nt; i++)
-            for (int j = s0; j <= i; j++) {
-                std::vector<int> ks;
-                for (int k = 0; k < s0; k++)
-                    if (in_env(i, k) && in_env(j, k)) ks.push_back(k);
-                if (ks.empty()) continue;
-                work += (long long)ks.size();
-                pairs.push_back(i);
-                pairs.push_back(j);
-                kl.push_back(std::move(ks));
-            }
-        const int kc = (int)std::max<long long>(2, (work + d->ncu - 1) / std::max(1, d->ncu));
-        for (size_t p = 0; p < kl.size(); p++) {
-            for (size_t q = 0; q < kl[p].size(); q += kc) {
-                rec.push_back((int)p);
-                rec.push_back((int)klist.size());
-                const int cnt = (int)std::min<size_t>(kc, kl[p].size() - q);
-                rec.push_back(cnt);
-                klist.insert(klist.end(), kl[p].begin() + q, kl[p].begin() + q + cnt);
-            }
-            pptr.push_back((int)rec.size() / 3);
-        }
-        d->fl_syrk = (double)work * 2.0 * NB * NB * NB +
-                     (double)(pairs.size() / 2) * 2.0 * NB * NB;
-        d->nd_npair = (int)pairs.size() / 2;
-        d->nd_nrec = (int)rec.size() / 3;
         auto up = [&](int **dst, const std::vector<int> &v) -> int {
             TRY_RC(dev_alloc(dst, sizeof(int) * (v.size() + 1)));
-            if (!v.empty())
-                VLGBA_CHECK(hipMemcpyAsync(*dst, v.data(), sizeof(int) * v.size(),
-                                           hipMemcpyHostToDevice, d->stream));
-            return 0;
+            return put(*dst, v);
         };
-        TRY_RC(up(&d->nd_crow, crow));
-        TRY_RC(up(&d->nd_prow, prow));
-        TRY_RC(up(&d->nd_rowsrc, rowsrc));
-        TRY_RC(up(&d->nd_pair, pairs));
-        TRY_RC(up(&d->nd_pptr, pptr));
-        TRY_RC(up(&d->nd_rec, rec));
-        TRY_RC(up(&d->nd_klist, klist));
-        TRY_RC(dev_alloc(&d->nd_rhs, sizeof(double) * (size_t)d->slds));
-        TRY_RC(dev_alloc(&d->nd_x, sizeof(double) * (size_t)d->slds));
-        TRY_RC(dev_alloc(&d->nd_part, sizeof(double) * ((size_t)d->nd_nrec + 1) * (NB * NB + NB)));
+        TRY_RC(up(&d->nd_crow, P.crow));
+        TRY_RC(up(&d->nd_prow, P.prow));
+        TRY_RC(up(&d->nd_rowsrc, P.rowsrc));
+        TRY_RC(up(&d->nd_pair, P.pairs));
+        TRY_RC(up(&d->nd_pptr, P.pptr));
+        TRY_RC(up(&d->nd_rec, P.rec));
+        TRY_RC(up(&d->nd_klist, P.klist));
+        TRY_RC(dev_alloc(&d->nd_rhs, sizeof(double) * (size_t)P.slds));
+        TRY_RC(dev_alloc(&d->nd_x, sizeof(double) * (size_t)P.slds));
+        TRY_RC(dev_alloc(&d->nd_part, sizeof(double) * ((size_t)P.nd_nrec + 1) * (NB * NB + NB)));
         VLGBA_CHECK(hipStreamSynchronize(d->stream));
     }
-    {   // the envelope's algorithmic flops (see ba_dev::fl_factor; the CR's: above)
-        const double t = NB;
-        const double potri = 2.0 * t * t * t / 3.0, gemm = 2.0 * t * t * t, gemv = 2.0 * t * t;
-        for (int k = 0; k < nt && !d->cr_nlev && d->dense_solve != 3; k++) {
-            const double T = ptr[k + 1] - ptr[k];
-            // factor + inverse, y_k, T panels and their rhs updates, the trailing
-            // pairs of column k (applied in step k + 1; an arc column's separator
-            // x separator pairs go to the separator SYRK instead)
-            double nsr = 0;
-            if (nd && k < s0)
-                for (int q = ptr[k]; q < ptr[k + 1]; q++) nsr += list[q] >= s0;
-            d->fl_factor += potri + gemv + T * (gemm + gemv) +
-                            (T * (T + 1) / 2 - nsr * (nsr + 1) / 2) * gemm;
-            d->fl_back += (T + 1) * gemv;
-        }
-        if (d->cr_nlev > 0 && d->cr_fused) {   // one CR launch: timed as k_cr_factor
-            d->fl_factor += d->fl_back;
-            d->fl_back = 0.0;
-        }
-    }
-    d->pan_ptr_h = new int[nt + 1];
-    for (int k = 0; k <= nt; k++) d->pan_ptr_h[k] = ptr[k];
-    d->h_pan_list = new int[list.size() + 1];
-    for (size_t q = 0; q < list.size(); q++) d->h_pan_list[q] = list[q];
-    TRY_RC(dev_alloc(&d->pan_list, sizeof(int) * (list.size() + 1)));
-    if (!d->cr_nlev && d->dense_solve != 3 && nt <= d->ncu) {   // one-launch backward
+    TRY_RC(dev_alloc(&d->pan_list, sizeof(int) * (P.pan_list.size() + 1)));
+    if (P.back_one_launch) {
         TRY_RC(dev_alloc(&d->pan_ptr, sizeof(int) * (nt + 1)));
-        VLGBA_CHECK(hipMemcpyAsync(d->pan_ptr, ptr.data(), sizeof(int) * (nt + 1),
-                                   hipMemcpyHostToDevice, d->stream));
+        TRY_RC(put(d->pan_ptr, P.pan_ptr));
         TRY_RC(dev_alloc(&d->xgran64, sizeof(unsigned long long) * 128 * (size_t)nt));
         VLGBA_CHECK(hipMemsetAsync(d->xgran64, 0, sizeof(unsigned long long) * 128 * (size_t)nt,
                                    d->stream));
         d->back_epoch = 0;
     }
-    if (!d->cr_nlev && d->dense_solve != 3) {   // the factor's in-launch hand-off
+    if (P.handoff) {   // the factor's in-launch hand-off
         TRY_RC(dev_alloc(&d->kflag, sizeof(unsigned) * (size_t)nt));
         VLGBA_CHECK(hipMemsetAsync(d->kflag, 0, sizeof(unsigned) * (size_t)nt, d->stream));
         d->fac_epoch = 0;
         // runner mode's flags: lflag | dflag | uflag | pflag, nt each, then
         // the runner's timeout word.  Opt-in (VLGBA_ENV_RUNNER=1): the runner
         // makes progress only while its stream has a hardware queue of its own
-        const char *er = std::getenv("VLGBA_ENV_RUNNER");
-        d->env_runner = er && er[0] == '1';
-        if (d->env_runner && d->pan_ptr) {
+        if (P.runner_flags) {
             const size_t nw = 4 * (size_t)nt + 1;
             TRY_RC(dev_alloc(&d->rflag, sizeof(unsigned) * nw));
             VLGBA_CHECK(hipMemsetAsync(d->rflag, 0, sizeof(unsigned) * nw, d->stream));
         }
     }
-    TRY_RC(dev_alloc(&d->env_tiles, sizeof(int) * (env.size() + 1)));
-    if (!list.empty())
-        VLGBA_CHECK(hipMemcpyAsync(d->pan_list, list.data(), sizeof(int) * list.size(),
-                                   hipMemcpyHostToDevice, d->stream));
-    VLGBA_CHECK(hipMemcpyAsync(d->env_tiles, env.data(), sizeof(int) * env.size(),
+    TRY_RC(dev_alloc(&d->env_tiles, sizeof(int) * (P.env.size() + 1)));
+    TRY_RC(put(d->pan_list, P.pan_list));
+    VLGBA_CHECK(hipMemcpyAsync(d->env_tiles, P.env.data(), sizeof(int) * P.env.size(),
                                hipMemcpyHostToDevice, d->stream));
     VLGBA_CHECK(hipMemsetAsync(d->S, 0, sizeof(double) * sdim * sdim, d->stream));
     VLGBA_CHECK(hipStreamSynchronize(d->stream));
     return 0;
 }
 
+// also after a setup that returned early: every pointer is null or owned
 void ba_chol_free(ba_dev *d)
 {
-    for (void *q : {(void *)d->S, (void *)d->linv, (void *)d->ywork, (void *)d->nd_crow,
-                    (void *)d->nd_prow, (void *)d->nd_rowsrc, (void *)d->nd_rhs, (void *)d->nd_x,
-                    (void *)d->nd_pair, (void *)d->nd_pptr, (void *)d->nd_rec, (void *)d->nd_klist,
-                    (void *)d->nd_part})
-        if (q) ba_dfree(q);
-    d->S = d->linv = d->ywork = d->nd_rhs = d->nd_x = d->nd_part = nullptr;
-    d->nd_crow = d->nd_prow = d->nd_rowsrc = d->nd_pair = d->nd_pptr = d->nd_rec = d->nd_klist =
-        nullptr;
+    void **dev[] = {(void **)&d->S, (void **)&d->linv, (void **)&d->ywork, (void **)&d->nd_crow,
+                    (void **)&d->nd_prow, (void **)&d->nd_rowsrc, (void **)&d->nd_rhs,
+                    (void **)&d->nd_x, (void **)&d->nd_pair, (void **)&d->nd_pptr,
+                    (void **)&d->nd_rec, (void **)&d->nd_klist, (void **)&d->nd_part,
+                    (void **)&d->xgran, (void **)&d->rflag, (void **)&d->crflag, (void **)&d->crf,
+                    (void **)&d->crs, (void **)&d->cr_elim, (void **)&d->cr_keep, (void **)&d->crL,
+                    (void **)&d->tb_ptr, (void **)&d->tb_blk, (void **)&d->pan_list,
+                    (void **)&d->pan_ptr, (void **)&d->xgran64, (void **)&d->kflag,
+                    (void **)&d->env_tiles};
+    for (void **q : dev) {
+        if (*q) ba_dfree(*q);
+        *q = nullptr;
+    }
+    delete d->plan;
+    d->plan = nullptr;
     d->nd_np = 0;
-    delete[] d->h_tfirst;
-    delete[] d->pan_ptr_h;
-    delete[] d->h_pan_list;
-    d->h_pan_list = nullptr;
-    delete[] d->cr_eptr_h;
-    delete[] d->cr_kptr_h;
-    d->cr_eptr_h = d->cr_kptr_h = nullptr;
-    if (d->xgran) ba_dfree(d->xgran);
-    d->xgran = nullptr;
-    if (d->rflag) ba_dfree(d->rflag);
-    d->rflag = nullptr;
-    d->rstream = nullptr;   // the process's (env_runner_stream)
-    if (d->crflag) ba_dfree(d->crflag);
-    d->crflag = nullptr;
     d->cr_fused = 0;
-    if (d->crf) ba_dfree(d->crf);
-    if (d->crs) ba_dfree(d->crs);
-    delete[] d->crf_ptr_h;
-    delete[] d->crs_ptr_h;
-    d->crf = d->crs = nullptr;
-    d->crf_ptr_h = d->crs_ptr_h = nullptr;
-    if (d->cr_elim) ba_dfree(d->cr_elim);
-    if (d->cr_keep) ba_dfree(d->cr_keep);
-    if (d->crL) ba_dfree(d->crL);
-    d->cr_elim = d->cr_keep = nullptr;
-    d->crL = nullptr;
     d->cr_nlev = 0;
-    if (d->tb_ptr) ba_dfree(d->tb_ptr);
-    if (d->tb_blk) ba_dfree(d->tb_blk);
-    d->tb_ptr = d->tb_blk = nullptr;
-    if (d->pan_list) ba_dfree(d->pan_list);
-    if (d->pan_ptr) ba_dfree(d->pan_ptr);
-    if (d->xgran64) ba_dfree(d->xgran64);
-    if (d->kflag) ba_dfree(d->kflag);
-    d->pan_ptr = nullptr;
-    d->xgran64 = nullptr;
-    d->kflag = nullptr;
-    if (d->env_tiles) ba_dfree(d->env_tiles);
-    d->h_tfirst = d->pan_ptr_h = nullptr;
-    d->pan_list = d->env_tiles = nullptr;
+    d->rstream = nullptr;   // the process's (env_runner_stream)
 }
 
 int ba_assemble_tiles(ba_dev *d)
@@ -3768,11 +3328,12 @@ static int envelope_columns(ba_dev *d, int k0, int k1, long long L, double *rhs,
         Rn.k1[0] = k1;
         if (env_runner_start(d, Rn, L, rhs)) run = false;
     }
+    const std::vector<int> &pan_ptr = d->plan->pan_ptr, &pan_list = d->plan->pan_list;
     for (int k = k0; k < k1; k++) {
-        const int p0 = d->pan_ptr_h[k], T = d->pan_ptr_h[k + 1] - p0;
-        const int q0 = k > k0 ? d->pan_ptr_h[k - 1] : 0, Tp = k > k0 ? p0 - q0 : 0;
+        const int p0 = pan_ptr[k], T = pan_ptr[k + 1] - p0;
+        const int q0 = k > k0 ? pan_ptr[k - 1] : 0, Tp = k > k0 ? p0 - q0 : 0;
         // column k-1's trailing pairs below row k (see k_factor_step)
-        const int kin = Tp > 0 && d->h_pan_list[q0] == k;
+        const int kin = Tp > 0 && pan_list[q0] == k;
         const int Tr = Tp - kin, ntr = Tr * (Tr + 1) / 2;
         const int nw = ntr;   // one workgroup per trailing pair
         KT_B(d);
@@ -3801,7 +3362,7 @@ static int envelope_backward(ba_dev *d, long long L, double *x, int nospin)
         return -(int)hipGetLastError();
     }
     for (int k = nt - 1; k >= 0; k--) {
-        const int j0 = d->h_tfirst[k];
+        const int j0 = d->plan->tfirst[k];
         KT_B(d);
         k_backward<<<k - j0 + 1, 256, 0, d->stream>>>(d->S, L, k, j0, d->linv, d->ywork, x);
         KT_E(d, KT_BACKWARD);
@@ -3814,6 +3375,8 @@ int ba_chol_solve(ba_dev *d, int nospin)
     const int nt = d->nt;
     d->camupd_done = 0;   // only the one-launch CR below does the camera update
     const size_t smem3 = sizeof(double) * 3 * NB * LP;
+    const std::vector<int> &eptr = d->plan->eptr, &kptr = d->plan->kptr;
+    const std::vector<int> &fptr = d->plan->fptr, &sptr = d->plan->sptr;
     TRY_RC(ba_ensure_dyn_lds((const void *)k_factor_step, smem3));
     TRY_RC(ba_ensure_dyn_lds((const void *)k_cr_factor, smem3));
     TRY_RC(ba_ensure_dyn_lds((const void *)k_cr_update, smem3));
@@ -3825,22 +3388,8 @@ int ba_chol_solve(ba_dev *d, int nospin)
         return -(int)hipGetLastError();
     }
     if (d->cr_nlev > 0 && d->cr32 && d->cr_fused && d->crflag && !nospin) {   // one launch
-        const int nl = d->cr_nlev, nrec = d->cr_eptr_h[nl];
-        cr32_fplan P{};
-        P.nl = nl;
-        P.nrec = nrec;
-        P.l0two = 3 * d->cr_eptr_h[1] > d->ncu;
-        P.b0[0] = 0;
-        P.b0[1] = (P.l0two ? 2 : 3) * d->cr_eptr_h[1];
-        for (int l = 1; l < nl; l++) {
-            const int nf = d->crf_ptr_h[l + 1] - d->crf_ptr_h[l];
-            const int ns = d->crs_ptr_h[l + 1] - d->crs_ptr_h[l];
-            P.fofs[l] = d->crf_ptr_h[l];
-            P.sofs[l] = d->crs_ptr_h[l];
-            P.b0[l + 1] = P.b0[l] + 3 * nf + ns;
-        }
-        P.sofs[nl] = d->crs_ptr_h[nl];
-        for (int l = 0; l <= nl; l++) P.eofs[l] = d->cr_eptr_h[l];
+        const cr32_fplan &P = d->plan->fplan;
+        const int nl = P.nl, nrec = P.nrec;
         if (++d->back_epoch == 0) d->back_epoch = 1;
         cr32_camupd cu{};
         if (d->camupd_fold) {   // the next update launches no k_camera_update
@@ -3858,7 +3407,7 @@ int ba_chol_solve(ba_dev *d, int nospin)
         const int ncu32 = d->ncu;
         const int n32 = d->nt32, TB = d->tb32;
         {   // level 0 on the assembled S
-            const int ne = d->cr_eptr_h[1];
+            const int ne = eptr[1];
             const int fs = 3 * ne <= 2 * ncu32;   // ~60 KB LDS: two workgroups per CU
             KT_B(d);
             k_cr32_factor<<<fs ? 3 * ne : ne, 256, 0, d->stream>>>(
@@ -3868,15 +3417,15 @@ int ba_chol_solve(ba_dev *d, int nospin)
         }
         // levels >= 1: the previous level's update folded into the factor launch
         for (int l = 1; l < d->cr_nlev; l++) {
-            const int f0 = d->crf_ptr_h[l], ne = d->crf_ptr_h[l + 1] - f0;
-            const int s0 = d->crs_ptr_h[l], ns = d->crs_ptr_h[l + 1] - s0;
+            const int f0 = fptr[l], ne = fptr[l + 1] - f0;
+            const int s0 = sptr[l], ns = sptr[l + 1] - s0;
             KT_B(d);
             k_cr32_level<<<3 * ne + ns, 256, 0, d->stream>>>(
                 d->S, d->lds, TB, d->ld, d->crf + 5 * f0, ne, d->crs + 3 * s0, n32, d->linv,
                 d->crL, d->rhs, d->ywork, d->scal + 4);
             KT_E(d, KT_CR_FACTOR);
         }
-        const int nrec = d->cr_eptr_h[d->cr_nlev];
+        const int nrec = eptr[d->cr_nlev];
         if (d->xgran && nrec <= 2 * d->ncu && !nospin) {   // every record co-resident: one launch
             if (++d->back_epoch == 0) d->back_epoch = 1;
             KT_B(d);
@@ -3887,7 +3436,7 @@ int ba_chol_solve(ba_dev *d, int nospin)
             return -(int)hipGetLastError();
         }
         for (int l = d->cr_nlev - 1; l >= 0; l--) {
-            const int e0 = d->cr_eptr_h[l], ne = d->cr_eptr_h[l + 1] - e0;
+            const int e0 = eptr[l], ne = eptr[l + 1] - e0;
             KT_B(d);
             k_cr32_back<<<ne, 256, 0, d->stream>>>(d->cr_elim + 3 * e0, n32, TB, d->ld,
                                                    d->linv, d->crL, d->ywork, d->da);
@@ -3901,8 +3450,8 @@ int ba_chol_solve(ba_dev *d, int nospin)
         // workgroups -- the levels are latency bound, the chip mostly idle
         const int ncu = d->ncu;
         for (int l = 0; l < d->cr_nlev; l++) {
-            const int e0 = d->cr_eptr_h[l], ne = d->cr_eptr_h[l + 1] - e0;
-            const int k0 = d->cr_kptr_h[l], nk = d->cr_kptr_h[l + 1] - k0;
+            const int e0 = eptr[l], ne = eptr[l + 1] - e0;
+            const int k0 = kptr[l], nk = kptr[l + 1] - k0;
             const int fs = 5 * ne <= ncu, us = 4 * nk <= ncu;
             KT_B(d);
             k_cr_factor<<<fs ? 5 * ne : ne, 256, smem3, d->stream>>>(
@@ -3917,7 +3466,7 @@ int ba_chol_solve(ba_dev *d, int nospin)
             }
         }
         for (int l = d->cr_nlev - 1; l >= 0; l--) {
-            const int e0 = d->cr_eptr_h[l], ne = d->cr_eptr_h[l + 1] - e0;
+            const int e0 = eptr[l], ne = eptr[l + 1] - e0;
             KT_B(d);
             k_cr_back<<<ne, 256, 0, d->stream>>>(d->cr_elim + 3 * e0, nt, d->linv, d->crL,
                                                  d->ywork, d->da);
@@ -3945,52 +3494,9 @@ int ba_chol_solve(ba_dev *d, int nospin)
             if (env_runner_start(d, Rn, L, d->nd_rhs)) run = false;   // the launches alone
         }
         for (int st = 0; st < nsteps; st++) {
-            nd_step P{};
-            P.grouped = d->nd_grouped;
-            int nbk = 0;
-            for (int t = 0; t < np; t++) {
-                const int k = d->nd_a0[t] + st;
-                if (k >= d->nd_a0[t + 1]) continue;
-                const int p0 = d->pan_ptr_h[k], T = d->pan_ptr_h[k + 1] - p0;
-                const bool cont = k > d->nd_a0[t];   // not the arc's first column
-                const int q0 = cont ? d->pan_ptr_h[k - 1] : 0, Tp = cont ? p0 - q0 : 0;
-                const int kin = Tp > 0 && d->h_pan_list[q0] == k;
-                int nsr = 0;   // separator rows among column k-1's trailing rows
-                for (int q = q0 + kin; q < q0 + Tp; q++) nsr += d->h_pan_list[q] >= s0;
-                const int Tr = Tp - kin, u = P.np++;
-                P.k[u] = k;
-                P.T[u] = T;
-                P.Tp[u] = Tp;
-                P.pofs[u] = p0;
-                P.qofs[u] = q0;
-                const int ntr = Tr * (Tr + 1) / 2 - nsr * (nsr + 1) / 2;
-                P.ntr[u] = ntr;
-                P.kend[u] = run ? d->nd_a0[t + 1] : 0;
-                P.b0[u] = nbk;
-                P.pb[u + 1] = P.pb[u] + T;
-                nbk += 1 + T;
-            }
-            // the trailing workgroups: each arc's share of the cap (with the hand-off)
-            int ttot = 0;
-            for (int u = 0; u < P.np; u++) ttot += P.ntr[u];
-            const int tw = ttot;   // one workgroup per trailing pair
-            for (int u = 0; u < P.np; u++) {
-                const int nw = tw == ttot ? P.ntr[u]
-                                          : (P.ntr[u] == 0 ? 0
-                                                           : std::max(1, (int)((long long)tw *
-                                                                               P.ntr[u] / ttot)));
-                P.ts[u] = nw;
-                P.tb[u + 1] = P.tb[u] + nw;
-            }
-            if (!P.grouped) {   // arc-major: arc u's trailing workgroups follow its panels
-                int acc = 0;
-                for (int u = 0; u < P.np; u++) {
-                    P.b0[u] = acc;
-                    acc += 1 + P.T[u] + P.ts[u];
-                }
-            }
-            nbk += P.tb[P.np];
-            P.b0[P.np] = nbk;
+            nd_step P;
+            chol_nd_step(*d->plan, st, run, &P);
+            const int nbk = P.b0[P.np];
             KT_B(d);
             k_factor_multi<<<nbk, 256, kflag ? sizeof(double) * 2 * NB * LP : smem3, d->stream>>>(
                 d->S, L, d->pan_list, P, s0, d->linv,

@@ -22,6 +22,12 @@
 #include <hip/hip_runtime.h>
 #include <cstddef>
 #include <cstdint>
+// the chunk / group / long-track limits (BA_CH_*, BA_G*, BA_MF_*, BA_LONG_*,
+// BA_LCAM_LDS, BA_LMATCH_BATCH) and the reduced solve's (BA_TILE*, BA_ND_*,
+// BA_CR_MAXLEV): shared with the host planners
+#include "ba_limits.h"
+
+struct chol_plan;   // the reduced solve's host plan (ba_chol_plan.h)
 
 #define VLGBA_CHECK(x)                                                              \
     do {                                                                            \
@@ -68,14 +74,6 @@ struct ba_flags {
 #ifndef BA_FUSE_CAMRED
 #define BA_FUSE_CAMRED 1
 #endif
-// nested dissection of the envelope: at most this many camera arcs
-#ifndef BA_ND_MAX
-#define BA_ND_MAX 8
-#endif
-// ... and at most this many separator tile pairs (their SYRK partials: 33 KB
-// each) / host checks (pairs x arc tiles) in its setup, else the natural order
-#define BA_ND_MAX_PAIRS 16384LL
-#define BA_ND_MAX_SETUP (1LL << 26)
 // robust loss of the fast path (vlgba_set_loss; vlg_loss in ba_kernels.hip):
 // kind 0 none, 1 Huber, 2 Cauchy; c the scale in pixels
 struct ba_loss {
@@ -121,12 +119,14 @@ struct ba_dev {
     // tile envelope of the reduced system (64 x 64 tiles): tile row i of L is
     // non-zero only in tile columns >= tfirst[i] (profile is preserved by the
     // factorisation), so tiles left of it are never touched.
+    // The host plan of the solve (chol_plan_build, ba_chol_plan.cpp: tfirst, the
+    // panel lists, the CR records' level pointers, the launch plans) is *plan,
+    // owned by ba_chol_setup / ba_chol_free; the scalars other files read are
+    // mirrored in the fields below.
+    chol_plan *plan;
     int nt;
-    int *h_tfirst;     // host [nt]
-    int *pan_ptr_h;    // host [nt+1]  offsets into pan_list (panel tiles of step k)
-    int *h_pan_list;   // host copy of pan_list
     int *pan_list;     // device: tile rows i > k with tfirst[i] <= k, per k
-    int *pan_ptr;      // device copy of pan_ptr_h (k_backward_all)
+    int *pan_ptr;      // device [nt+1] offsets into pan_list (k_backward_all)
     unsigned long long *xgran64;  // [nt][128] x_k granules of the one-launch backward
     unsigned *kflag;   // [nt] envelope factor: L_kk^-1 / y_k published (epoch fac_epoch)
     unsigned fac_epoch;
@@ -145,7 +145,6 @@ struct ba_dev {
     // block cyclic reduction (tile-tridiagonal S): per level, eliminated tiles
     // (e, p, q) and kept tiles (k, e-, e+, k2); -1 = none
     int cr_nlev;
-    int *cr_eptr_h, *cr_kptr_h;   // host [nlev+1]
     int *cr_elim, *cr_keep;       // device [3 * ne], [4 * nk]
     double *crL;                  // [2][nt][64*64] L(p, e) | L(q, e)
     // camera-aligned cyclic reduction: tiles of tb32 = NA * floor(32 / NA)
@@ -156,7 +155,6 @@ struct ba_dev {
     int cr32, tb32, nt32;
     // fused levels (L >= 1): records (e, p, q, em, ep) and survivors (k, em, ep)
     int *crf, *crs;               // device
-    int *crf_ptr_h, *crs_ptr_h;   // host [nlev + 1], entries per level (level 0 empty)
     // one-launch back substitution (k_cr32_back_all): x of every tile as
     // 64 epoch-tagged 8-byte granules, read by the tiles of the level below
     unsigned long long *xgran;    // [nt32][64]
@@ -170,7 +168,7 @@ struct ba_dev {
     // writes each block's lower entries straight into S (and the pinv rule
     // of exactly-zero diagonals), so no k_assemble_tiles launch.  Needs every
     // lower entry of every diagonal CR tile covered by a block (asm_direct_ok,
-    // ba_chol_setup): the CR writes only those tiles, so S's other entries
+    // chol_plan_build): the CR writes only those tiles, so S's other entries
     // keep the zeros of the setup.
     int asm_direct_ok, asm_direct;
     // camera update inside the one-launch CR (k_cr32_fused, x = da in camera
@@ -183,7 +181,7 @@ struct ba_dev {
     // ba_launch_update (every other solve and every other writer of da clears
     // it: their update launches k_camera_update).
     int camupd_fold, camupd_done;
-    // one-level nested dissection of the envelope (ba_chol_setup, auto mode
+    // one-level nested dissection of the envelope (chol_plan_build, auto mode
     // when S is not tridiagonal; dense_solve 4 forces it): the cameras split
     // into nd_np arcs of consecutive cameras minus the separator (cameras
     // coupled to an earlier arc).  Rows: arc 0 | arc 1 | ... | separator, each
@@ -205,7 +203,7 @@ struct ba_dev {
     int *nd_rec;                  // device [nrec][3] (pair, kofs, kcnt)
     int *nd_klist;                // device: the arc columns of the records
     double *nd_part;              // [nrec][64*64 + 64] per-record L_i L_j^T | L_i y
-    // algorithmic flops of one reduced solve (ba_chol_setup; bench.py's roofline
+    // algorithmic flops of one reduced solve (chol_plan_build; bench.py's roofline
     // of the solve kernels): tile-dense potrf + trtri of the diagonal tiles,
     // panel / trailing / fill / SYRK GEMMs and the triangular GEMVs, each counted
     // once (the redundant factorisations of the role-split records are not).
@@ -331,9 +329,6 @@ struct ba_dev {
     do { if ((d)->kt && (d)->kt->on) kt_end((d)->kt, (d)->stream, (id)); } while (0)
 
 #define BA_PART_MAX 65536
-// the chunk / group / long-track limits (BA_CH_*, BA_G*, BA_MF_*, BA_LONG_*,
-// BA_LCAM_LDS, BA_LMATCH_BATCH): shared with the host planner
-#include "ba_limits.h"
 
 // ---- ba_kernels.hip ----
 int ba_launch_rotations(ba_dev *d, const double *a, double *rot, int all5);

@@ -1,7 +1,24 @@
-// ba_limits.h -- chunk / group / long-track limits of the fast Schur path,
-// shared by the kernels (through ba_internal.h) and the host planner
-// (ba_plan.h).  Macros only: no HIP header, so host-only code can include it.
+// ba_limits.h -- chunk / group / long-track limits of the fast Schur path and
+// the tile heights / nested-dissection / cyclic-reduction limits of the reduced
+// solve, shared by the kernels (through ba_internal.h) and the host planners
+// (ba_plan.h, ba_chol_plan.h).  Macros only: no HIP header, so host-only code
+// can include it.
 #pragma once
+
+// reduced solve (ba_chol.hip, ba_chol_plan.cpp): rows of a Cholesky tile and of
+// a camera-aligned cyclic-reduction tile (padded to it in LDS)
+#define BA_TILE 64
+#define BA_TILE32 32
+// nested dissection of the envelope: at most this many camera arcs
+#ifndef BA_ND_MAX
+#define BA_ND_MAX 8
+#endif
+// ... and at most this many separator tile pairs (their SYRK partials: 33 KB
+// each) / host checks (pairs x arc tiles) in its setup, else the natural order
+#define BA_ND_MAX_PAIRS 16384LL
+#define BA_ND_MAX_SETUP (1LL << 26)
+// the one-launch cyclic reduction (k_cr32_fused) holds at most this many levels
+#define BA_CR_MAXLEV 30
 
 #ifndef BA_CH_OBS
 #define BA_CH_OBS 128      // observations per Schur chunk (LDS budget)

@@ -15,6 +15,7 @@
 // dense solve, and a 3-scalar all-reduce drives the accept/reject decision.
 #include "ba_internal.h"
 #include "ba_plan.h"   // the host planner: sort_obs, order_points_by_kind, plan_host
+#include "ba_chol_plan.h"   // the reduced solve's plan (ba_dev::plan)
 #include "../../include/vlgba.h"
 
 #include <rccl/rccl.h>
@@ -707,7 +708,7 @@ static int ctx_setup(vlgba_ctx *c, const vlgba_problem *p, const host_obs &h,
     TRY(ctx_alloc(c, &d.term, 2 * (size_t)d.T));
     TRY(upload(d.blk_jk, hb.jk.data(), hb.jk.size(), s));
     // the long tracks' pair counts per block (k_long_pairs) on the device while
-    // the host builds the solve's structure (ba_chol_setup); read back below
+    // the host builds the solve's structure (chol_plan_build); read back below
     int *lp_cnt = nullptr;
     if (fast && d.nl > 0) {
         TRY(ctx_alloc(c, &lp_cnt, (size_t)d.nb + 1));
@@ -1333,7 +1334,7 @@ static int lm_pass(vlgba_ctx *c, int relinearize, vlgba_step_info *info)
         }
         if (kt) {
             kt->nev = 0;
-            // the solve's algorithmic flops (ba_chol_setup's count) on the timers
+            // the solve's algorithmic flops (chol_plan_build's count) on the timers
             // that ran them: one-launch / per-level CR, or the envelope's steps,
             // separator SYRK and backward solve
             const bool cr = d.cr_nlev > 0;
@@ -2018,8 +2019,8 @@ int vlgba_plan_info(vlgba_ctx *c, long long *info, int len)
 {
     if (!c || !info) return VLGBA_E_ARG;
     const ba_dev &d = c->d;
-    const long long ne = d.cr_nlev ? d.cr_eptr_h[d.cr_nlev] : 0;
-    const long long nk = d.cr_nlev ? d.cr_kptr_h[d.cr_nlev] : 0;
+    const long long ne = d.cr_nlev ? d.plan->eptr[d.cr_nlev] : 0;
+    const long long nk = d.cr_nlev ? d.plan->kptr[d.cr_nlev] : 0;
     const long long v[VLGBA_NPLAN] = {d.N,   d.n,    d.m,   d.na,         d.nch,  d.ns,
                                       d.nes, d.ngrp, d.ngs, d.nge,        d.nb,   d.nt,
                                       d.cr_nlev, ne, nk,    d.ordered,    d.ordered ? d.T : d.nterm_fast,

@@ -1,5 +1,5 @@
-"""The envelope Cholesky on a nested-dissection camera order (ba_chol.hip:
-ba_chol_setup's planner, k_factor_multi, k_sep_update / k_sep_reduce,
+"""The envelope Cholesky on a nested-dissection camera order (ba_chol_plan.cpp's
+planner; ba_chol.hip: k_factor_multi, k_sep_update / k_sep_reduce,
 k_nd_scatter).  The cameras split into arcs of consecutive cameras and a
 separator (cameras co-visible with an earlier arc); the arcs' columns are
 factored side by side, then the separator.  A different elimination order

@@ -1,4 +1,4 @@
-"""The nested-dissection planner of the envelope solve (ba_chol.hip
+"""The nested-dissection planner of the envelope solve (ba_chol_plan.cpp
 nd_choose, through the host-only vlgba_debug_nd_plan: no GPU).  The cameras
 split into arcs [bnd[t], bnd[t+1]); a camera co-visible with a camera of an
 earlier arc joins the separator.  Checked: no co-visible pair crosses two

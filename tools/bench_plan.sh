@@ -1,13 +1,18 @@
 #!/bin/bash
 # Build tools/build/bench_plan (the CPU harness of the context's host planner:
 # tools/bench_plan.cpp + csrc/ba_plan.cpp, host compiler only, with the
-# planner's phase times on stderr), and write the problem files it reads
+# planner's phase times on stderr) and tools/build/bench_chol_plan (the reduced
+# solve's planner: tools/bench_chol_plan.cpp + csrc/ba_plan.cpp +
+# csrc/ba_chol_plan.cpp), and write the problem files they read
 # (tools/build/plan_*.bin).
 set -e
 cd "$(dirname "$0")/.."
 mkdir -p tools/build
 ${CXX:-c++} -O3 -std=c++17 -ffp-contract=off -DBA_PLAN_TIMING -I include -pthread \
   tools/bench_plan.cpp bundleadjustmentmatlab_amd/csrc/ba_plan.cpp -o tools/build/bench_plan
+${CXX:-c++} -O3 -std=c++17 -ffp-contract=off -I include -pthread \
+  tools/bench_chol_plan.cpp bundleadjustmentmatlab_amd/csrc/ba_plan.cpp \
+  bundleadjustmentmatlab_amd/csrc/ba_chol_plan.cpp -o tools/build/bench_chol_plan
 python3 - <<'PY'
 import sys
 import numpy as np
