@@ -30,6 +30,7 @@ class VlgbaProblem(ctypes.Structure):
 
 MODEL_EUCLIDEAN, MODEL_PROJECTIVE = 0, 1   # VLGBA_MODEL_*
 LOSSES = {"none": 0, "huber": 1, "cauchy": 2}   # VLGBA_LOSS_*
+JACOBIANS = {"fd": 0, "analytic": 1}            # VLGBA_JAC_*
 
 
 class VlgbaOptions(ctypes.Structure):
@@ -100,6 +101,8 @@ SIGNATURES = {
     "vlgba_covariance": (c_int, [ctypes.c_void_p, c_int, c_dp, c_dp, c_dp, c_dp]),
     "vlgba_set_loss": (c_int, [ctypes.c_void_p, c_int, c_double]),
     "vlgba_get_loss": (c_int, [ctypes.c_void_p, c_ip, c_dp]),
+    "vlgba_set_jacobian": (c_int, [ctypes.c_void_p, c_int]),
+    "vlgba_get_jacobian": (c_int, [ctypes.c_void_p, c_ip]),
     "vlgba_get_residuals": (c_int, [ctypes.c_void_p, c_dp, c_dp, c_dp]),
     "vlgba_sync": (c_int, [ctypes.c_void_p]),
     "vlgba_destroy": (None, [ctypes.c_void_p]),

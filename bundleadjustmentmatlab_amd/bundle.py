@@ -25,7 +25,7 @@ from __future__ import annotations
 import ctypes
 import numpy as np
 
-from ._lib import (ALLREDUCE_FN, LOSSES, MODEL_EUCLIDEAN, MODEL_PROJECTIVE, NKERNELS, ON_PASS_FN,
+from ._lib import (ALLREDUCE_FN, JACOBIANS, LOSSES, MODEL_EUCLIDEAN, MODEL_PROJECTIVE, NKERNELS, ON_PASS_FN,
                    VlgbaOptions,
                    VlgbaProblem, VlgbaResectProblem, VlgbaStats,
                    VlgbaStepInfo, c_dp, c_ip, c_up, check, lib)
@@ -211,6 +211,15 @@ class BundleAdjuster:
     ``loss`` ("none", "huber" or "cauchy") with ``loss_scale`` in pixels makes
     the solve robust (set_loss; vlgba_set_loss): error_ and the pass scalars
     are then the robust cost.  Not with ``parity`` / ``ordered``.
+    ``jacobian`` is "fd" (the reference's forward differences, h = 1e-10) or
+    "analytic" (closed-form derivatives on the fast path: set_jacobian;
+    vlgba_set_jacobian) -- the same residuals and cost, Jacobians without the
+    differences' ~1e-6 noise, and a camera at w = 0 can rotate.  None (the
+    default) leaves the library's default: "fd", or "analytic" where the
+    environment variable VLGBA_JACOBIAN=analytic is set; a given value wins over
+    the environment.  Not with ``parity`` / ``ordered`` (ValueError); on a
+    problem that the planner hands to the ordered kernels all the same
+    (plan_info()["ordered"] == 1) "analytic" raises VlgbaError -1001.
     """
     SOLVERS = {"auto": 0, "dense": 1, "envelope": 2, "sequential": 3, "nd": 4}
     SCHUR_KERNELS = {"auto": 0, "terms": 1}
@@ -222,8 +231,14 @@ class BundleAdjuster:
                  rank=0, world_size=1, comm_id=None, max_iter=0, max_iter2=0, lambda0=0.0,
                  dense_solve=False, ordered=False, allreduce=None, solver=None,
                  schur_kernel="auto", semantics="mex", model="euclidean", m=None,
-                 parity=False, stop_rel=0.0, log=None, loss="none", loss_scale=0.0):
+                 parity=False, stop_rel=0.0, log=None, loss="none", loss_scale=0.0,
+                 jacobian=None):
         L = lib()
+        if jacobian is not None and jacobian not in JACOBIANS:
+            raise ValueError(f"jacobian must be one of {sorted(JACOBIANS)}")
+        if jacobian == "analytic" and (parity or ordered):
+            raise ValueError("analytic Jacobians do not go with parity / ordered mode (bit "
+                             "parity with the reference's forward differences)")
         if loss not in LOSSES:
             raise ValueError(f"loss must be one of {sorted(LOSSES)}")
         if loss != "none" and (parity or ordered):
@@ -281,12 +296,14 @@ class BundleAdjuster:
               "vlgba_create")
         self._h = h
         self._L = L
-        if loss != "none":
-            try:
+        try:
+            if loss != "none":
                 self.set_loss(loss, loss_scale)
-            except Exception:
-                self.close()
-                raise
+            if jacobian is not None and self.get_jacobian() != jacobian:
+                self.set_jacobian(jacobian)       # (over the environment's default)
+        except Exception:
+            self.close()
+            raise
 
     def set_loss(self, loss="none", scale=0.0):
         """The robust loss of the passes from here on (vlgba_set_loss): "none",
@@ -302,6 +319,19 @@ class BundleAdjuster:
         check(self._L.vlgba_get_loss(self._h, ctypes.byref(kind), ctypes.byref(scale)),
               "vlgba_get_loss")
         return {v: k for k, v in LOSSES.items()}[kind.value], scale.value
+
+    def set_jacobian(self, jacobian="fd"):
+        """The Jacobians of the passes from here on (vlgba_set_jacobian): "fd" or
+        "analytic".  The next pass or getter linearises again."""
+        if jacobian not in JACOBIANS:
+            raise ValueError(f"jacobian must be one of {sorted(JACOBIANS)}")
+        check(self._L.vlgba_set_jacobian(self._h, JACOBIANS[jacobian]), "vlgba_set_jacobian")
+
+    def get_jacobian(self):
+        """"fd" or "analytic" (vlgba_get_jacobian)."""
+        kind = ctypes.c_int()
+        check(self._L.vlgba_get_jacobian(self._h, ctypes.byref(kind)), "vlgba_get_jacobian")
+        return {v: k for k, v in JACOBIANS.items()}[kind.value]
 
     def residuals(self):
         """Per observation at the current parameters (vlgba_get_residuals), in
@@ -487,7 +517,7 @@ class BundleAdjuster:
 # ---------------------------------------------------------------------------
 def euclid_obs_adjuster(K, m, n, obs_pt, obs_cam, obs_x, *varargin, num_vis=0.0, device=0,
                         rank=0, world_size=1, comm_id=None, semantics="mex", loss="none",
-                        loss_scale=0.0, **solver):
+                        loss_scale=0.0, jacobian=None, **solver):
     """The BundleAdjuster that bundle_euclid_obs would create for this problem
     and these options (its structure only: no parameter values), so a caller
     can build it ahead of time -- the host plan of vlgba_create runs with the
@@ -499,15 +529,16 @@ def euclid_obs_adjuster(K, m, n, obs_pt, obs_cam, obs_x, *varargin, num_vis=0.0,
                         pivot=o["pivot"] if o["fix_pivot"] else None, verbose=o["verbose"],
                         num_vis=num_vis, device=device, rank=rank, world_size=world_size,
                         comm_id=comm_id, semantics=semantics, loss=loss, loss_scale=loss_scale,
-                        **solver)
+                        jacobian=jacobian, **solver)
     ba.fingerprint = _adjuster_fingerprint(K, m, n, obs_pt, obs_cam, obs_x, o, num_vis,
                                            semantics, rank, world_size, device, comm_id,
-                                           loss, loss_scale)
+                                           loss, loss_scale, ba.get_jacobian())
     return ba
 
 
 def _adjuster_fingerprint(K, m, n, obs_pt, obs_cam, obs_x, o, num_vis, semantics, rank,
-                          world_size, device, comm_id, loss="none", loss_scale=0.0):
+                          world_size, device, comm_id, loss="none", loss_scale=0.0,
+                          jacobian="fd"):
     """What a prebuilt adjuster was made for: sizes, the parsed
     options, K, a hash of the observation list, the device and the RCCL id
     -- a context built for another subset, other options, another GPU or
@@ -531,14 +562,17 @@ def _adjuster_fingerprint(K, m, n, obs_pt, obs_cam, obs_x, o, num_vis, semantics
     return (int(m), int(n), int(o["num_variableK"]), bool(o["fix_structure"]),
             bool(o["fix_motion"]), bool(o["fix_pivot"]), bool(o["verbose"]), float(num_vis),
             semantics, int(rank), int(world_size), int(device), comm_id is not None,
-            h.hexdigest(), str(loss), float(loss_scale) if loss != "none" else 0.0)
+            h.hexdigest(), str(loss), float(loss_scale) if loss != "none" else 0.0,
+            str(jacobian))
 
 
 def bundle_euclid_obs(K, Te, w, Xe, obs_pt, obs_cam, obs_x, *varargin, num_vis=0.0, device=0,
                       rank=0, world_size=1, comm_id=None, return_stats=False,
                       semantics="mex", adjuster=None, return_covariance=False, loss="none",
-                      loss_scale=0.0, **solver):
+                      loss_scale=0.0, jacobian=None, **solver):
     """bundle_euclid on a COO observation list (0-based point / camera ids).
+    ``jacobian``: "fd", "analytic" or None (BundleAdjuster); a prebuilt adjuster
+    must have been made in the mode asked for here (None: its own).
     ``loss`` / ``loss_scale``: the robust loss (BundleAdjuster); error_ is then
     the robust cost / num_vis, and a returned covariance is the unscaled one.
     ``solver`` keywords go to BundleAdjuster (parity, stop_rel, max_iter,
@@ -560,7 +594,9 @@ def bundle_euclid_obs(K, Te, w, Xe, obs_pt, obs_cam, obs_x, *varargin, num_vis=0
             raise ValueError("bundle_euclid_obs: solver options belong to the prebuilt adjuster")
         ba = adjuster.result() if hasattr(adjuster, "result") else adjuster
         want = _adjuster_fingerprint(K, m, n, obs_pt, obs_cam, obs_x, o, num_vis, semantics,
-                                     rank, world_size, device, comm_id, loss, loss_scale)
+                                     rank, world_size, device, comm_id, loss, loss_scale,
+                                     jacobian if jacobian is not None else
+                                     ba.get_jacobian())
         if getattr(ba, "fingerprint", None) != want:
             ba.close()
             raise ValueError("bundle_euclid_obs: the prebuilt adjuster is for another problem "
@@ -569,7 +605,7 @@ def bundle_euclid_obs(K, Te, w, Xe, obs_pt, obs_cam, obs_x, *varargin, num_vis=0
         ba = euclid_obs_adjuster(K, m, n, obs_pt, obs_cam, obs_x, *varargin, num_vis=num_vis,
                                  device=device, rank=rank, world_size=world_size,
                                  comm_id=comm_id, semantics=semantics, loss=loss,
-                                 loss_scale=loss_scale, **solver)
+                                 loss_scale=loss_scale, jacobian=jacobian, **solver)
     with ba:
         ba.set_params(a, b)
         err, st = ba.run()
@@ -586,7 +622,8 @@ def bundle_euclid_obs(K, Te, w, Xe, obs_pt, obs_cam, obs_x, *varargin, num_vis=0
 def bundle_euclid(K, Te, w, Xe, x, *varargin, device=0, return_stats=False, semantics="mex",
                   return_covariance=False, loss="none", loss_scale=0.0, **solver):
     """[K_ Te_ w_ Xe_ error_] = bundle_euclid(K, Te, w, Xe, x, ...)  (bundle_euclid.m:1);
-    ``loss`` / ``loss_scale`` as bundle_euclid_obs."""
+    ``loss`` / ``loss_scale`` and ``jacobian="fd" | "analytic"`` (one of the
+    solver keywords) as bundle_euclid_obs."""
     x = _F(x)
     m, n = np.shape(w)[1], x.shape[1]
     o = parse_options(m, n, varargin, x=x, nomex=semantics == "nomex")

@@ -18,6 +18,8 @@
 //                         as a0 + h * da (mex_bundle_1 :30-33, proj :47-51)
 //   project_col(c, b, x)  column c of [A | B]: c < NA as project_dcam, else
 //                         proj(a0, b + h e_{c-NA}) (mex_bundle_1 :59-66)
+//   jac_columns(b, half, row)  analytic-Jacobian mode: the closed-form columns
+//                         of [A | B] (rot then holds R(w), dR/dw_k, 0)
 // -------------------------------------------------------------------------
 template <int NA, bool PROJ = (NA == BA_PROJ_NA)>
 struct cam_view;
@@ -81,6 +83,53 @@ struct cam_view<NA, false> {
         for (int q = 0; q < 9; q++) Rk[q] = Rs[q];
         vlg_project(Kc1, Rk, a1 + 3, b1, x);
     }
+    // Analytic-Jacobian mode (the table's slots 1..3 hold dR/dw_k,
+    // rotation_k_jac): the closed-form columns of [A | B] into row.  With
+    // Xc = R b + t, z = Xc_2, u = Xc_0 / z, v = Xc_1 / z:
+    //   J = dx/dXc = [fx/z 0 -fx u/z; 0 fy/z -fy v/z],  J d = (fx/z (d0 - u d2),
+    //   fy/z (d1 - v d2));  A_wk = J (dR_k b), A_T = J, B = J R, and the
+    //   calibration columns d x / d f = (u, v) (NA = 7), d x / d (fx fy cx cy)
+    //   = (u, 0), (0, v), (1, 0), (0, 1) (NA = 10).
+    // Lane 0 of the observation's pair forms the rotation columns, lane 1 the
+    // rest (jac_lane1).
+    __device__ __forceinline__ void jac_columns(const double b[3], int half, double *row) const
+    {
+        double S[3];
+        vlg_rot_b(Rl, b, S);
+        const double X0 = S[0] + a0[3], X1 = S[1] + a0[4], z = S[2] + a0[5];
+        const double iz = 1.0 / z;
+        const double u = X0 * iz, v = X1 * iz, fxz = Kc[0] * iz, fyz = Kc[4] * iz;
+        if (!half) {
+#pragma unroll
+            for (int k = 0; k < 3; k++) {
+                const double *D = R + 9 * (1 + k);
+                double d[3];
+                vlg_rot_b(D, b, d);
+                row[2 * k] = fxz * (d[0] - u * d[2]);
+                row[2 * k + 1] = fyz * (d[1] - v * d[2]);
+            }
+        } else {
+            row[6] = fxz;  row[7] = 0.0;
+            row[8] = 0.0;  row[9] = fyz;
+            row[10] = -(fxz * u);
+            row[11] = -(fyz * v);
+            if constexpr (NA == 7) {
+                row[12] = u;  row[13] = v;
+            }
+            if constexpr (NA == 10) {
+                row[12] = u;    row[13] = 0.0;
+                row[14] = 0.0;  row[15] = v;
+                row[16] = 1.0;  row[17] = 0.0;
+                row[18] = 0.0;  row[19] = 1.0;
+            }
+#pragma unroll
+            for (int k = 0; k < 3; k++) {
+                row[2 * NA + 2 * k] = fxz * (Rl[3 * k] - u * Rl[3 * k + 2]);
+                row[2 * NA + 2 * k + 1] = fyz * (Rl[3 * k + 1] - v * Rl[3 * k + 2]);
+            }
+        }
+    }
+    static __device__ __forceinline__ constexpr bool jac_lane1(int col) { return col >= 3; }
 };
 
 template <int NA>
@@ -115,6 +164,36 @@ struct cam_view<NA, true> {
             b1[c] = cam ? b[c] : b[c] + H_FD * ((c == col - NA) ? 1.0 : 0.0);
         vlg_project_proj(a1, b1, x);
     }
+    // Analytic-Jacobian mode: the quotient rule on x_ = P [b; 1], x = x_(1:2) /
+    // x_(3).  With bh = [b; 1], iz = 1 / x_2, u = x_0 iz, v = x_1 iz the column
+    // of P(i, j) (index i + 3 j) is (bh_j iz, 0), (0, bh_j iz), -(bh_j iz) (u, v)
+    // for i = 0, 1, 2, and B_k = iz (P(0,k) - u P(2,k), P(1,k) - v P(2,k)).
+    // Lane 0: columns j = 0, 1 of P; lane 1: j = 2, 3 and B.
+    __device__ __forceinline__ void jac_columns(const double b[3], int half, double *row) const
+    {
+        const double *P = a0;
+        const double x0 = P[0] * b[0] + P[3] * b[1] + P[6] * b[2] + P[9];
+        const double x1 = P[1] * b[0] + P[4] * b[1] + P[7] * b[2] + P[10];
+        const double x2 = P[2] * b[0] + P[5] * b[1] + P[8] * b[2] + P[11];
+        const double iz = 1.0 / x2, u = x0 * iz, v = x1 * iz;
+#pragma unroll
+        for (int jj = 0; jj < 2; jj++) {
+            const int j = 2 * half + jj;
+            const double g = (j == 0 ? b[0] : j == 1 ? b[1] : j == 2 ? b[2] : 1.0) * iz;
+            double *r = row + 6 * j;
+            r[0] = g;         r[1] = 0.0;
+            r[2] = 0.0;       r[3] = g;
+            r[4] = -(g * u);  r[5] = -(g * v);
+        }
+        if (half) {
+#pragma unroll
+            for (int k = 0; k < 3; k++) {
+                row[2 * NA + 2 * k] = iz * (P[3 * k] - u * P[3 * k + 2]);
+                row[2 * NA + 2 * k + 1] = iz * (P[3 * k + 1] - v * P[3 * k + 2]);
+            }
+        }
+    }
+    static __device__ __forceinline__ constexpr bool jac_lane1(int col) { return col >= 6; }
 };
 
 // -------------------------------------------------------------------------
@@ -129,6 +208,28 @@ __device__ __forceinline__ void rotation_k(const double w[3], int k, double *__r
     vlg_rodrigues(R, w1);
 #pragma unroll
     for (int q = 0; q < 9; q++) out[9 * k + q] = R[q];
+}
+
+// Analytic-Jacobian mode (ba_dev::jac): slot 0 R(w) as above, bit for bit;
+// slots 1..3 dR/dw_k (vlg_drodrigues); slot 4 unused, zero.
+__device__ __forceinline__ void rotation_k_jac(const double w[3], int k, double *__restrict__ out)
+{
+    if (k == 0) {
+        rotation_k(w, k, out);
+        return;
+    }
+    double D[9];
+#pragma unroll
+    for (int q = 0; q < 9; q++) D[q] = 0.0;
+    if (k < 4) vlg_drodrigues(D, w, k - 1);
+#pragma unroll
+    for (int q = 0; q < 9; q++) out[9 * k + q] = D[q];
+}
+
+__device__ __forceinline__ void rotations5_jac(const double w[3], double *__restrict__ out)
+{
+#pragma unroll
+    for (int k = 0; k < 5; k++) rotation_k_jac(w, k, out);
 }
 
 __device__ __forceinline__ void rotations5(const double w[3], double *__restrict__ out)

@@ -2614,6 +2614,11 @@ struct cr32_camupd {
     int na, m;
 };
 
+// JAC: the folded camera update builds the analytic-Jacobian mode's table
+// (rotation_k_jac); everything else is the same code.  (A template of the
+// kernel itself, not a body shared by two kernels: with the record pool's
+// static LDS declared in a device function the compiler allocated 8 KB more.)
+template <bool JAC>
 __global__ __launch_bounds__(256) void k_cr32_fused(double *S, long long lds, int TB, long long ld,
                                                     const int *__restrict__ elim,
                                                     const int *__restrict__ frec,
@@ -2747,7 +2752,10 @@ __global__ __launch_bounds__(256) void k_cr32_fused(double *S, long long lds, in
                 if (ck == 0) cu.a_new[(size_t)cu.na * cj + cc] = av[cc];
             }
         }
-        rotation_k(av, ck, cu.rot_new + 45 * (size_t)cj);
+        if constexpr (JAC)
+            rotation_k_jac(av, ck, cu.rot_new + 45 * (size_t)cj);
+        else
+            rotation_k(av, ck, cu.rot_new + 45 * (size_t)cj);
     }
     CR_ST(3);
 }
@@ -3397,9 +3405,16 @@ int ba_chol_solve(ba_dev *d, int nospin)
             d->camupd_done = 1;
         }
         KT_B(d);
-        k_cr32_fused<<<P.b0[nl] + nrec, 256, 0, d->stream>>>(
-            d->S, d->lds, d->tb32, d->ld, d->cr_elim, d->crf, d->crs, d->nt32, d->linv, d->crL,
-            d->rhs, d->ywork, d->da, d->crflag, d->xgran, d->back_epoch, d->scal + 4, P, cu);
+        if (d->jac)
+            k_cr32_fused<true><<<P.b0[nl] + nrec, 256, 0, d->stream>>>(
+                d->S, d->lds, d->tb32, d->ld, d->cr_elim, d->crf, d->crs, d->nt32, d->linv,
+                d->crL, d->rhs, d->ywork, d->da, d->crflag, d->xgran, d->back_epoch,
+                d->scal + 4, P, cu);
+        else
+            k_cr32_fused<false><<<P.b0[nl] + nrec, 256, 0, d->stream>>>(
+                d->S, d->lds, d->tb32, d->ld, d->cr_elim, d->crf, d->crs, d->nt32, d->linv,
+                d->crL, d->rhs, d->ywork, d->da, d->crflag, d->xgran, d->back_epoch,
+                d->scal + 4, P, cu);
         KT_E(d, KT_CR_FACTOR);
         return -(int)hipGetLastError();
     }

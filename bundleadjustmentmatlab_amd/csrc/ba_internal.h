@@ -232,6 +232,12 @@ struct ba_dev {
     // when loss_kind != 0, else the plain ones
     int loss_kind;
     double loss_scale;
+    // Jacobians of the fast-path linearisation (vlgba_set_jacobian): 0 the
+    // reference's forward differences, 1 closed form -- rot / rot_new then hold
+    // R(w), dR/dw_k, 0 per camera (rotation_k_jac) and the linearisation
+    // kernels' JAC instantiations run, k_camera_update_jac / k_cr32_fused<true>
+    // build the table of a_new.
+    int jac;
     int ndb;           // camera parameters in the back substitution: 6 (MEX, App. A
                        // Q3) or NA (bundle_euclid_nomex.m semantics)
     int nch;           // chunks

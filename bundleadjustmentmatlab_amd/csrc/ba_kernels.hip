@@ -10,6 +10,8 @@
 //   k_damp_point       bundle_euclid.m:168-184 (V* = damp(V), pinv, Y = W V*^-1)
 //   k_schur            mex_bundle_2_Se_.c:72-155 (S_jk, e_) on the co-visible blocks
 //   k_linearize_chunk  fast path: linearisation per chunk of points + U/eA partials
+//   k_*_jac            the analytic-Jacobian mode's twins (closed-form columns of
+//                      [A | B], rotation table R(w), dR/dw_k): beyond the reference
 //   k_schur_group      fast path: damp + V*^-1 + Y + S / e_ partials per group of chunks
 //   k_assemble         dense S for the reduced solve (bundle_euclid.m:193)
 //   k_camera_update    mex_bundle_3_db_new.c:137-140 (a_new) + rotations of a_new
@@ -172,6 +174,17 @@ __global__ void k_rotations(const double *__restrict__ a, double *__restrict__ r
     const double *aj = a + (size_t)NA * j;
     const double w[3] = {aj[0], aj[1], aj[2]};
     rotations5(w, rot + 45 * (size_t)j);
+}
+
+// analytic-Jacobian mode (ba_dev::jac): R(w), dR/dw_k, 0 (rotations5_jac)
+template <int NA>
+__global__ void k_rotations_jac(const double *__restrict__ a, double *__restrict__ rot, int m)
+{
+    const int j = blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= m) return;
+    const double *aj = a + (size_t)NA * j;
+    const double w[3] = {aj[0], aj[1], aj[2]};
+    rotations5_jac(w, rot + 45 * (size_t)j);
 }
 
 // device sin / cos of the rotations (vlg_libm.h), exported for the parity
@@ -362,7 +375,11 @@ struct ba_upd {
 // sqrt(w), rho(s) into the chunk's cost partial (vlg_loss); everything after
 // the row -- W, V, eB, the U / eA partials -- is then the weighted normal
 // equations' without another change.  LOSS = false is the plain body.
-template <int NA, bool UPD, bool LOSS>
+// JAC = true (vlgba_set_jacobian, VLGBA_JAC_ANALYTIC): the FD columns of the
+// row are replaced by the closed-form ones (cam_view::jac_columns; rot holds
+// dR/dw_k in slots 1..3).  The base projection, so x_hat, e and the SSE, and
+// everything after the row are the same code.
+template <int NA, bool UPD, bool LOSS, bool JAC = false>
 __device__ __forceinline__ void linearize_chunk_body(
     const int *__restrict__ ch_pt, const int *__restrict__ ch_obase,
     const int *__restrict__ ch_eslot, const int *__restrict__ eslot_optr,
@@ -609,7 +626,21 @@ __device__ __forceinline__ void linearize_chunk_body(
             for (int c = 0; c < 3; c++) bi[c] = UPD ? bu[c] : b[3 * (size_t)i + c];
             double xh[2];
             double *row = rows + RS * lo;
-            if constexpr (NA == 6) {
+            if constexpr (JAC && NA == 6) {
+                auto proj6 = [&](const double *rt, int jr) {
+                    cam_view<NA> cv6(a, K4, rt, jr, j);
+                    cv6.project(bi, xh);
+                    cv6.jac_columns(bi, half, row);
+                };
+                if (NCAMS > 0 && camst)
+                    proj6(&camr[0], j - cam_lo);
+                else
+                    proj6(rot, j);
+            } else if constexpr (JAC) {
+                cam_view<NA> cv(a, K4, rot, j);
+                cv.project(bi, xh);
+                cv.jac_columns(bi, half, row);
+            } else if constexpr (NA == 6) {
                 // the rotations from LDS (staged) or the table: one code path
                 // each, so every load has its address space at compile time
                 auto proj6 = [&](const double *rt, int jr) {
@@ -648,7 +679,9 @@ __device__ __forceinline__ void linearize_chunk_body(
                 vlg_loss(ls.kind, ls.c, e0 * e0 + e1 * e1, &rho, &sw);
 #pragma unroll
                 for (int col = 0; col < NA + 3; col++) {
-                    const bool lane1 = NA == 6 ? (col == 4 || col > 5) : col >= NC0;
+                    const bool lane1 = JAC      ? cam_view<NA>::jac_lane1(col)
+                                       : NA == 6 ? (col == 4 || col > 5)
+                                                 : col >= NC0;
                     if (lane1 == (half != 0)) {
                         row[2 * col] *= sw;
                         row[2 * col + 1] *= sw;
@@ -823,6 +856,22 @@ __global__ __launch_bounds__(256, (NA == 6) ? BA_LIN_WAVES : 1) void k_update_li
     BA_LIN_ARGS, ba_upd u, ba_loss ls)
 {
     linearize_chunk_body<NA, true, true>(BA_LIN_PASS, u, blockIdx.x, ls);
+}
+
+// the two with the closed-form Jacobian columns (JAC = true; ls unused without
+// LOSS)
+template <int NA, bool LOSS>
+__global__ __launch_bounds__(256, (NA == 6) ? BA_LIN_WAVES : 1) void k_linearize_chunk_jac(
+    BA_LIN_ARGS, ba_loss ls)
+{
+    linearize_chunk_body<NA, false, LOSS, true>(BA_LIN_PASS, ba_upd{}, blockIdx.x, ls);
+}
+
+template <int NA, bool LOSS>
+__global__ __launch_bounds__(256, (NA == 6) ? BA_LIN_WAVES : 1) void k_update_linearize_jac(
+    BA_LIN_ARGS, ba_upd u, ba_loss ls)
+{
+    linearize_chunk_body<NA, true, LOSS, true>(BA_LIN_PASS, u, blockIdx.x, ls);
 }
 
 // U_j, eA_j from the per-chunk partials (fast path).  One 256-lane workgroup
@@ -2032,8 +2081,9 @@ __global__ void k_assemble(const int *__restrict__ blk_jk, const double *__restr
 // rotation launch), and the camera part of dp'(lambda dp + g)
 // (bundle_euclid.m:215-217), one partial per 64-lane workgroup.
 // -------------------------------------------------------------------------
-template <int NA>
-__global__ __launch_bounds__(320) void k_camera_update(
+// JAC: the table of the analytic-Jacobian mode (rotation_k_jac)
+template <int NA, bool JAC>
+__device__ __forceinline__ void camera_update_body(
     const double *__restrict__ a, const double *__restrict__ da,
     const double *__restrict__ eA, int m, double lambda, double *__restrict__ a_new,
     double *__restrict__ rot_new, double *__restrict__ part)
@@ -2056,13 +2106,36 @@ __global__ __launch_bounds__(320) void k_camera_update(
                 acc += d * (lambda * d + eA[(size_t)NA * j + c]);
             }
         }
-        if constexpr (NA != BA_PROJ_NA) rotation_k(an, k, rot_new + 45 * (size_t)j);
+        if constexpr (NA != BA_PROJ_NA) {
+            if constexpr (JAC)
+                rotation_k_jac(an, k, rot_new + 45 * (size_t)j);
+            else
+                rotation_k(an, k, rot_new + 45 * (size_t)j);
+        }
     }
     if (k == 0) {
 #pragma unroll
         for (int off = 32; off > 0; off >>= 1) acc += __shfl_down(acc, off, 64);
         if (lane == 0) part[blockIdx.x] = acc;
     }
+}
+
+template <int NA>
+__global__ __launch_bounds__(320) void k_camera_update(
+    const double *__restrict__ a, const double *__restrict__ da,
+    const double *__restrict__ eA, int m, double lambda, double *__restrict__ a_new,
+    double *__restrict__ rot_new, double *__restrict__ part)
+{
+    camera_update_body<NA, false>(a, da, eA, m, lambda, a_new, rot_new, part);
+}
+
+template <int NA>
+__global__ __launch_bounds__(320) void k_camera_update_jac(
+    const double *__restrict__ a, const double *__restrict__ da,
+    const double *__restrict__ eA, int m, double lambda, double *__restrict__ a_new,
+    double *__restrict__ rot_new, double *__restrict__ part)
+{
+    camera_update_body<NA, true>(a, da, eA, m, lambda, a_new, rot_new, part);
 }
 
 // -------------------------------------------------------------------------
@@ -2621,7 +2694,11 @@ int ba_launch_rotations(ba_dev *d, const double *a, double *rot, int all5)
     if (d->na == BA_PROJ_NA) return 0;   // projective camera: no rotations
     const int g = grid_for(d->m, 64, 1 << 30);
     KT_B(d);
-    BA_DISPATCH(d->na, (k_rotations<NA><<<g, 64, 0, d->stream>>>(a, rot, d->m)));
+    if (d->jac) {
+        BA_DISPATCH(d->na, (k_rotations_jac<NA><<<g, 64, 0, d->stream>>>(a, rot, d->m)));
+    } else {
+        BA_DISPATCH(d->na, (k_rotations<NA><<<g, 64, 0, d->stream>>>(a, rot, d->m)));
+    }
     KT_E(d, KT_ROT);
     return -(int)hipGetLastError();
 }
@@ -2634,26 +2711,23 @@ static void lin_chunk_launch(ba_dev *d, ba_flags f, const double *a, const doubl
                              double *chsse, const ba_upd *u)
 {
     const ba_loss ls{d->loss_kind, d->loss_scale};
-    if (u && ls.kind)
-        k_update_linearize_loss<NA><<<d->nch, 256, 0, d->stream>>>(
-            d->ch_pt, d->ch_obase, d->ch_eslot, d->eslot_optr, d->eslot_obs, d->pt_ptr,
-            d->obs_cam, d->obs_lpt, d->obs_x, d->K4, a, rot, b, f, d->pivot, W, V, eB, upart,
-            chsse, d->nch_reg, d->seg_pt, d->vseg, d->ch_cam, *u, ls);
-    else if (u)
-        k_update_linearize<NA><<<d->nch, 256, 0, d->stream>>>(
-            d->ch_pt, d->ch_obase, d->ch_eslot, d->eslot_optr, d->eslot_obs, d->pt_ptr,
-            d->obs_cam, d->obs_lpt, d->obs_x, d->K4, a, rot, b, f, d->pivot, W, V, eB, upart,
-            chsse, d->nch_reg, d->seg_pt, d->vseg, d->ch_cam, *u);
-    else if (ls.kind)
-        k_linearize_chunk_loss<NA><<<d->nch, 256, 0, d->stream>>>(
-            d->ch_pt, d->ch_obase, d->ch_eslot, d->eslot_optr, d->eslot_obs, d->pt_ptr,
-            d->obs_cam, d->obs_lpt, d->obs_x, d->K4, a, rot, b, f, d->pivot, W, V, eB, upart,
-            chsse, d->nch_reg, d->seg_pt, d->vseg, d->ch_cam, ls);
-    else
-        k_linearize_chunk<NA><<<d->nch, 256, 0, d->stream>>>(
-            d->ch_pt, d->ch_obase, d->ch_eslot, d->eslot_optr, d->eslot_obs, d->pt_ptr,
-            d->obs_cam, d->obs_lpt, d->obs_x, d->K4, a, rot, b, f, d->pivot, W, V, eB, upart,
-            chsse, d->nch_reg, d->seg_pt, d->vseg, d->ch_cam);
+    // the launch shape and the leading arguments every instantiation shares
+#define LIN_GRID <<<d->nch, 256, 0, d->stream>>>
+#define LIN_ARGS                                                                           \
+    d->ch_pt, d->ch_obase, d->ch_eslot, d->eslot_optr, d->eslot_obs, d->pt_ptr, d->obs_cam, \
+        d->obs_lpt, d->obs_x, d->K4, a, rot, b, f, d->pivot, W, V, eB, upart, chsse,       \
+        d->nch_reg, d->seg_pt, d->vseg, d->ch_cam
+    if (d->jac) {   // closed-form columns (rot: R(w), dR/dw_k); the loss by template
+        if (u && ls.kind) k_update_linearize_jac<NA, true> LIN_GRID(LIN_ARGS, *u, ls);
+        else if (u) k_update_linearize_jac<NA, false> LIN_GRID(LIN_ARGS, *u, ls);
+        else if (ls.kind) k_linearize_chunk_jac<NA, true> LIN_GRID(LIN_ARGS, ls);
+        else k_linearize_chunk_jac<NA, false> LIN_GRID(LIN_ARGS, ls);
+    } else if (u && ls.kind) k_update_linearize_loss<NA> LIN_GRID(LIN_ARGS, *u, ls);
+    else if (u) k_update_linearize<NA> LIN_GRID(LIN_ARGS, *u);
+    else if (ls.kind) k_linearize_chunk_loss<NA> LIN_GRID(LIN_ARGS, ls);
+    else k_linearize_chunk<NA> LIN_GRID(LIN_ARGS);
+#undef LIN_ARGS
+#undef LIN_GRID
 }
 
 int ba_launch_linearize(ba_dev *d, ba_flags f)
@@ -2896,15 +2970,28 @@ static void sum3_camera_dpg(ba_dev *d, double lam_dpg, ba_sum3 *s3)
     s3->cam_lambda = lam_dpg;
 }
 
+// k_camera_update, or its analytic-Jacobian twin (ba_dev::jac)
+static int launch_camera_update(ba_dev *d, int gc, double lam_dpg)
+{
+    if (d->jac) {
+        BA_DISPATCH(d->na, (k_camera_update_jac<NA><<<gc, 320, 0, d->stream>>>(
+                               d->a, d->da, d->eA, d->m, lam_dpg, d->a_new, d->rot_new,
+                               d->part)));
+    } else {
+        BA_DISPATCH(d->na, (k_camera_update<NA><<<gc, 320, 0, d->stream>>>(
+                               d->a, d->da, d->eA, d->m, lam_dpg, d->a_new, d->rot_new,
+                               d->part)));
+    }
+    return 0;
+}
+
 static int launch_update_fused(ba_dev *d, double lambda, ba_flags f, bool folded)
 {
     const int gc = (d->m + 63) / 64;
     const double lam_dpg = d->dpg_lambda ? lambda : 0.0;
     if (!folded) {   // (folded: a_new and rot_new are the solve's, ba_dev::camupd_done)
         KT_B(d);
-        BA_DISPATCH(d->na, (k_camera_update<NA><<<gc, 320, 0, d->stream>>>(
-                               d->a, d->da, d->eA, d->m, lam_dpg, d->a_new, d->rot_new,
-                               d->part)));
+        if (const int rc = launch_camera_update(d, gc, lam_dpg)) return rc;
         KT_E(d, KT_CAMUPD);
     }
     KT_B(d);
@@ -2952,9 +3039,7 @@ int ba_launch_update(ba_dev *d, double lambda, ba_flags f)
     const double lam_dpg = d->dpg_lambda ? lambda : 0.0;
     if (!folded) {
         KT_B(d);
-        BA_DISPATCH(d->na, (k_camera_update<NA><<<gc, 320, 0, d->stream>>>(
-                               d->a, d->da, d->eA, d->m, lam_dpg, d->a_new, d->rot_new,
-                               d->part)));
+        if (const int rc = launch_camera_update(d, gc, lam_dpg)) return rc;
         KT_E(d, KT_CAMUPD);
     }
     if (chunked) {

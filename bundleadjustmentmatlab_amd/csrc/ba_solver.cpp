@@ -577,6 +577,10 @@ static int ctx_setup(vlgba_ctx *c, const vlgba_problem *p, const host_obs &h,
               [](const char *w) { ST_MARK(w); });
     d.mfma = fast && plan.nch_mf > 0;
     if (!fast) d.ordered = 1;
+    // the ordered kernels read the table's slots 1..4 as R(w + h e_k): a context
+    // the planner hands to them keeps the forward differences, whatever
+    // VLGBA_JACOBIAN asked for (vlgba_set_jacobian refuses it afterwards)
+    if (d.ordered) d.jac = VLGBA_JAC_FD;
     ST_MARK("plan");
     d.nb = (int)hb.jk.size() / 2;
     d.T = (long long)hb.term.size() / 2;
@@ -929,6 +933,13 @@ static int ctx_create(const vlgba_problem *p, const vlgba_options *o, vlgba_ctx 
         c->d.ndb = o->semantics == 1 ? p->num_a : 6;
         c->d.loss_kind = VLGBA_LOSS_NONE;   // vlgba_set_loss
         c->d.loss_scale = 0.0;
+        c->d.jac = VLGBA_JAC_FD;            // vlgba_set_jacobian
+        if (const char *ev = std::getenv("VLGBA_JACOBIAN")) {
+            // the default of a fast-path context (ordered / parity and the stage
+            // entries keep the reference's forward differences)
+            if (!std::strcmp(ev, "analytic") && o->ordered == 0 && !stage_mode)
+                c->d.jac = VLGBA_JAC_ANALYTIC;
+        }
         rc = ctx_setup(c, p, h, pt_ptr_all, lower_blocks, all_diag, stage_mode);
         if (rc) break;
         ST_MARK("setup_end");
@@ -1864,6 +1875,28 @@ int vlgba_set_loss(vlgba_ctx *c, int kind, double scale)
     c->d.loss_kind = kind;
     c->d.loss_scale = kind != VLGBA_LOSS_NONE ? scale : 0.0;
     c->lin_valid = 0;   // the next pass / getter linearises with the new weights
+    return 0;
+}
+
+int vlgba_set_jacobian(vlgba_ctx *c, int kind)
+{
+    if (!c || (kind != VLGBA_JAC_FD && kind != VLGBA_JAC_ANALYTIC)) return VLGBA_E_ARG;
+    // ordered / parity mode exists for bit parity with the reference's differences
+    if (c->d.ordered) return VLGBA_E_ARG;
+    TRY(ctx_enter(c));
+    c->d.jac = kind;
+    // the table of the current a in the new mode's layout; a camera update the
+    // last solve folded in built the other one
+    TRY(ba_launch_rotations(&c->d, c->d.a, c->d.rot, 1));
+    c->lin_valid = 0;
+    c->d.camupd_done = 0;
+    return 0;
+}
+
+int vlgba_get_jacobian(vlgba_ctx *c, int *kind)
+{
+    if (!c) return VLGBA_E_ARG;
+    if (kind) *kind = c->d.jac;
     return 0;
 }
 

@@ -23,6 +23,8 @@
  *                           per-observation loop without changing a bit)
  *   vlg_project_proj        reproject_projective_point of
  *                           toolbox/bundle/mex_bundle_proj_1_XABeUVWeAeB.c:13-32
+ *   vlg_drodrigues          dR/dw_k of the exponential map (analytic-Jacobian
+ *                           mode; not part of the reference)
  *   vlg_fd_quot             (x1 - x0) / h without a division, bit-identical
  *   vlg_pinv3               3x3 pseudo-inverse of the damped point blocks
  *
@@ -81,6 +83,70 @@ VLG_HD void vlg_rodrigues(double R[9], const double om[3])
     R[6] = sth * y + mcth * xz;
     R[7] = -sth * x + mcth * yz;
     R[8] = 1 - mcth * (xx + yy);
+}
+
+/* ---- dR/dw_k of the exponential map (analytic-Jacobian mode) ---------------
+ * R = I + A K + B K^2, K = [w]x, A = sin th / th, B = (1 - cos th) / th^2 and
+ * K^2 = w w' - th^2 I, so with a1 = A'(th) / th, b1 = B'(th) / th
+ *   dR/dw_k = w_k a1 K + A G_k + w_k b1 K^2 + B (e_k w' + w e_k' - 2 w_k I),
+ * G_k = [e_k]x.  Below VLG_DROD_SERIES the four coefficients are their Taylor
+ * series in th^2: the closed forms a1 = (th cos th - sin th) / th^3 and
+ * b1 = (th sin th - 2 (1 - cos th)) / th^4 cancel to a relative error of about
+ * 3 u / th^2 and 12 u / th^2 (48 u at the switch-over, th = 0.5), while the
+ * series' first dropped term there is below 1e-17 of the sum.  th < 1e-6:
+ * vlg_rodrigues returns exactly I; the derivative is the limit G_k all the
+ * same, so a camera at w = 0 can rotate.  Column major dR[i + 3*j].          */
+#define VLG_DROD_SERIES 0.5
+VLG_HD void vlg_drodrigues(double dR[9], const double om[3], int k)
+{
+    const double x = om[0], y = om[1], z = om[2];
+    const double t2 = x * x + y * y + z * z;
+    const double th = sqrt(t2);
+    const double wk = k == 0 ? x : (k == 1 ? y : z);
+    double A, B, a1, b1;
+    if (th < 1e-6) {
+        A = 1.0; B = 0.0; a1 = 0.0; b1 = 0.0;
+    } else if (th < VLG_DROD_SERIES) {
+        /* sum_n (-1)^n t2^n / (2n+1)!, / (2n+2)!, and their th-derivatives / th */
+        A = 1.0 + t2 * (-1.0 / 6 + t2 * (1.0 / 120 + t2 * (-1.0 / 5040 + t2 * (1.0 / 362880 +
+            t2 * (-1.0 / 39916800 + t2 * (1.0 / 6227020800.0 + t2 * (-1.0 / 1307674368000.0)))))));
+        B = 0.5 + t2 * (-1.0 / 24 + t2 * (1.0 / 720 + t2 * (-1.0 / 40320 + t2 * (1.0 / 3628800 +
+            t2 * (-1.0 / 479001600 + t2 * (1.0 / 87178291200.0 + t2 * (-1.0 / 20922789888000.0)))))));
+        a1 = -1.0 / 3 + t2 * (1.0 / 30 + t2 * (-1.0 / 840 + t2 * (1.0 / 45360 +
+             t2 * (-1.0 / 3991680 + t2 * (1.0 / 518918400 + t2 * (-1.0 / 93405312000.0))))));
+        b1 = -1.0 / 12 + t2 * (1.0 / 180 + t2 * (-1.0 / 6720 + t2 * (1.0 / 453600 +
+             t2 * (-1.0 / 47900160 + t2 * (1.0 / 7264857600.0 + t2 * (-1.0 / 1494484992000.0))))));
+    } else {
+        const double s = VLG_SIN(th), c = VLG_COS(th), mc = 1.0 - c;
+        A = s / th;
+        B = mc / t2;
+        a1 = (th * c - s) / (t2 * th);
+        b1 = (th * s - 2.0 * mc) / (t2 * t2);
+    }
+    {
+        const double p = wk * a1, q = wk * b1, d = -2.0 * wk * B - q * t2;
+        /* w_k a1 K + w_k b1 (w w' - th^2 I) + B (e_k w' + w e_k' - 2 w_k I) */
+        dR[0] = q * (x * x) + d;
+        dR[4] = q * (y * y) + d;
+        dR[8] = q * (z * z) + d;
+        dR[1] = q * (x * y) + p * z;
+        dR[3] = q * (x * y) - p * z;
+        dR[2] = q * (x * z) - p * y;
+        dR[6] = q * (x * z) + p * y;
+        dR[5] = q * (y * z) + p * x;
+        dR[7] = q * (y * z) - p * x;
+        /* + A G_k and the e_k rows / columns of B (e_k w' + w e_k') */
+        if (k == 0) {
+            dR[0] += 2.0 * (B * x); dR[1] += B * y; dR[3] += B * y; dR[2] += B * z; dR[6] += B * z;
+            dR[5] += A; dR[7] -= A;
+        } else if (k == 1) {
+            dR[4] += 2.0 * (B * y); dR[1] += B * x; dR[3] += B * x; dR[5] += B * z; dR[7] += B * z;
+            dR[6] += A; dR[2] -= A;
+        } else {
+            dR[8] += 2.0 * (B * z); dR[2] += B * x; dR[6] += B * x; dR[5] += B * y; dR[7] += B * y;
+            dR[1] += A; dR[3] -= A;
+        }
+    }
 }
 
 /* ---- calibration override: reproject_point.h:29-41 ----------------------

@@ -79,7 +79,9 @@ def bundle_projective_obs(Pp, Xp, obs_pt, obs_cam, obs_x, *varargin, num_vis=0.0
     """bundle_projective on a COO observation list (0-based point / camera ids);
     varargin takes 'fix_structure', 'fix_motion', 'verbose' (visibility is the
     list itself).  ``loss`` / ``loss_scale``: the robust loss (BundleAdjuster;
-    error_ is then the robust cost, a returned covariance the unscaled one).  ``return_covariance`` appends BundleAdjuster.covariance()
+    error_ is then the robust cost, a returned covariance the unscaled one).
+    ``jacobian="fd" | "analytic"`` (BundleAdjuster) goes with the solver
+    keywords.  ``return_covariance`` appends BundleAdjuster.covariance()
     at the returned parameters (the projective model fixes no gauge: expect
     VlgbaError -1007 or very large values unless the structure is fixed)."""
     Pp, Xp = _F(Pp), _F(Xp)

@@ -38,7 +38,8 @@ extern "C" {
  * envelope runner's launch count), vlgba_debug_force_status word 6; 6 =
  * vlgba_covariance, VLGBA_E_SINGULAR; 6 also covers the robust-loss entry
  * points added since (vlgba_set_loss, vlgba_get_loss, vlgba_get_residuals,
- * VLGBA_LOSS_*: entry points only, no struct changed).  Callers
+ * VLGBA_LOSS_*: entry points only, no struct changed) and the Jacobian-mode
+ * ones (vlgba_set_jacobian, vlgba_get_jacobian, VLGBA_JAC_*: likewise).  Callers
  * check it once at load time with VLGBA_ABI_CHECK() (the MEX gateways and the Python
  * loader do): the library compares the version and the struct sizes the
  * caller was compiled with against its own and returns 0 or VLGBA_E_ABI. */
@@ -209,7 +210,10 @@ int vlgba_step(vlgba_ctx *ctx, int relinearize, int update_lm, vlgba_step_info *
  * cameras ascending within a point) for this rank's points.  Any pointer may
  * be NULL.  Also marks the linearisation valid for the next vlgba_step.
  * With a loss set (vlgba_set_loss) these are the weighted quantities: every
- * observation's Jacobian rows and residual times sqrt(w). */
+ * observation's Jacobian rows and residual times sqrt(w).
+ * In analytic-Jacobian mode (vlgba_set_jacobian) A and B are the closed-form
+ * derivatives: U, V, W, eA, eB are exact to fp64 rounding instead of the
+ * forward differences' ~1e-6; the residuals in eA, eB are the same bits. */
 int vlgba_get_linearization(vlgba_ctx *ctx, double *U, double *eA, double *V, double *eB,
                             double *W);
 /* the LM loop from the context's parameters; error_out / error_cap as
@@ -261,7 +265,10 @@ int vlgba_get_reduced_system(vlgba_ctx *ctx, int *blk_jk, double *blocks, double
  * reference's forward differences (h = 1e-10): an unfixed gauge usually leaves
  * S0 ill-conditioned rather than exactly singular, the call then succeeds with
  * the large values that implies, and every value carries the Jacobians'
- * relative noise of about 1e-6.
+ * relative noise of about 1e-6.  In analytic-Jacobian mode
+ * (vlgba_set_jacobian) they are the closed-form derivatives: that noise is
+ * gone, and the rotation rows of a camera with |w| < 1e-6 are no longer zero,
+ * so they are not fixed rows.
  * One rank only: VLGBA_E_ARG for world_size > 1 (with or without a
  * communicator); VLGBA_E_ARG too when rocSOLVER or its dpotrf / dpotri are not
  * available.  Uses 8 ld^2 bytes of device scratch (the pinv fallback's
@@ -300,6 +307,34 @@ int vlgba_covariance(vlgba_ctx *ctx, int scale, double *cov_a, double *cov_a_ful
 #define VLGBA_LOSS_CAUCHY 2
 int vlgba_set_loss(vlgba_ctx *ctx, int kind, double scale);
 int vlgba_get_loss(vlgba_ctx *ctx, int *kind, double *scale);
+/* ---- Jacobians of the fused LM path -----------------------------------------
+ *   VLGBA_JAC_FD        the reference's forward differences, h = 1e-10 (default)
+ *   VLGBA_JAC_ANALYTIC  closed-form derivatives of the same projection
+ * The analytic mode changes only the Jacobian columns A, B of the fast path's
+ * linearisation: x_hat, the residuals, the SSE (vlgba_step_info.old_sse /
+ * new_sse at equal parameters) and vlgba_get_residuals are bit for bit those of
+ * VLGBA_JAC_FD.  The derivative of the rotation is that of the exponential
+ * map; for |w| < 1e-6, where the projection uses R = I exactly (vl_rodrigues),
+ * it is the limit [e_k]x -- so a camera that starts at w = 0 rotates, which
+ * under forward differences it never does (its rotation columns are exactly
+ * zero).  Composes with vlgba_set_loss and sharded contexts (every rank sets
+ * the same mode).
+ * vlgba_set_jacobian: VLGBA_E_ARG for an unknown kind and for a context that
+ * runs the ordered kernels: ordered or parity mode (vlgba_options.ordered != 0),
+ * and a problem that the planner hands to them although ordered == 0 was asked
+ * for (a track of more than 65535 views, long tracks of more than 2^26 terms
+ * in all; vlgba_plan_info [15] tells).  Rebuilds the rotation table of the
+ * current parameters and marks the linearisation stale.  VLGBA_JAC_FD restores
+ * the default solver exactly.  The environment variable VLGBA_JACOBIAN=analytic
+ * makes analytic the default of every context created with ordered == 0 that
+ * stays on the fast path; one the planner hands to the ordered kernels stays
+ * VLGBA_JAC_FD (vlgba_get_jacobian tells).  Not covered (forward differences always): ordered /
+ * parity mode, vlgba_resect, the vlgba_mex_bundle_* stage entries and the
+ * MATLAB drop-ins. */
+#define VLGBA_JAC_FD 0
+#define VLGBA_JAC_ANALYTIC 1
+int vlgba_set_jacobian(vlgba_ctx *ctx, int kind);
+int vlgba_get_jacobian(vlgba_ctx *ctx, int *kind);
 /* per observation of this rank at the context's current parameters, in the
  * order of vlgba_get_linearization's W rows (point-major, cameras ascending
  * within a point): e [2 x N_local] the unweighted residuals x - x_hat, w
