@@ -31,6 +31,7 @@ class VlgbaProblem(ctypes.Structure):
 MODEL_EUCLIDEAN, MODEL_PROJECTIVE = 0, 1   # VLGBA_MODEL_*
 LOSSES = {"none": 0, "huber": 1, "cauchy": 2}   # VLGBA_LOSS_*
 JACOBIANS = {"fd": 0, "analytic": 1}            # VLGBA_JAC_*
+COV_METHODS = {"dense": 0, "selected": 1}       # VLGBA_COV_*
 
 
 class VlgbaOptions(ctypes.Structure):
@@ -101,6 +102,9 @@ SIGNATURES = {
     "vlgba_covariance": (c_int, [ctypes.c_void_p, c_int, c_dp, c_dp, c_dp, c_dp]),
     "vlgba_set_loss": (c_int, [ctypes.c_void_p, c_int, c_double]),
     "vlgba_get_loss": (c_int, [ctypes.c_void_p, c_ip, c_dp]),
+    "vlgba_set_covariance_method": (c_int, [ctypes.c_void_p, c_int]),
+    "vlgba_get_covariance_method": (c_int, [ctypes.c_void_p, c_ip]),
+    "vlgba_get_covariance_blocks": (c_int, [ctypes.c_void_p, c_ip, c_dp]),
     "vlgba_set_jacobian": (c_int, [ctypes.c_void_p, c_int]),
     "vlgba_get_jacobian": (c_int, [ctypes.c_void_p, c_ip]),
     "vlgba_get_residuals": (c_int, [ctypes.c_void_p, c_dp, c_dp, c_dp]),
@@ -131,6 +135,7 @@ SIGNATURES = {
     "vlgba_debug_pinv_solve": (c_int, [c_int, c_dp, c_dp, c_dp]),
     "vlgba_debug_force_status": (c_int, [ctypes.c_void_p, c_int, c_int]),
     "vlgba_debug_nd_plan": (c_int, [c_int, c_int, c_ip, c_int, c_ip, c_ip]),
+    "vlgba_debug_selinv_plan": (c_int, [c_int, c_ip, c_ip, c_ip]),
 }
 
 ERRORS = {-1001: "bad argument",

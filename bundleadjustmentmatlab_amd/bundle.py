@@ -25,7 +25,7 @@ from __future__ import annotations
 import ctypes
 import numpy as np
 
-from ._lib import (ALLREDUCE_FN, JACOBIANS, LOSSES, MODEL_EUCLIDEAN, MODEL_PROJECTIVE, NKERNELS, ON_PASS_FN,
+from ._lib import (ALLREDUCE_FN, COV_METHODS, JACOBIANS, LOSSES, MODEL_EUCLIDEAN, MODEL_PROJECTIVE, NKERNELS, ON_PASS_FN,
                    VlgbaOptions,
                    VlgbaProblem, VlgbaResectProblem, VlgbaStats,
                    VlgbaStepInfo, c_dp, c_ip, c_up, check, lib)
@@ -437,28 +437,74 @@ class BundleAdjuster:
                 S[na * j:na * j + na, na * k:na * k + na] = B
         return S, e_
 
-    def covariance(self, scale=True, full=False):
+    def set_covariance_method(self, method="dense"):
+        """How covariance() forms the camera covariance from here on
+        (vlgba_set_covariance_method): "dense" (rocSOLVER inverse of the dense
+        reduced system, 8 ld^2 bytes of scratch) or "selected" (a selected
+        inverse on the camera-aligned cyclic reduction's factors: only the
+        co-visible blocks, three 32 x 32 tiles of scratch per reduction tile).
+        "selected" raises VlgbaError (-1001) unless plan_info() shows the
+        camera-aligned cyclic reduction (cr_levels > 0, cr_rows == num_a *
+        (32 // num_a)) on one rank outside ordered / parity mode."""
+        if method not in COV_METHODS:
+            raise ValueError(f"method must be one of {sorted(COV_METHODS)}")
+        check(self._L.vlgba_set_covariance_method(self._h, COV_METHODS[method]),
+              "vlgba_set_covariance_method")
+
+    def get_covariance_method(self):
+        """"dense" or "selected" (vlgba_get_covariance_method)."""
+        kind = ctypes.c_int()
+        check(self._L.vlgba_get_covariance_method(self._h, ctypes.byref(kind)),
+              "vlgba_get_covariance_method")
+        return {v: k for k, v in COV_METHODS.items()}[kind.value]
+
+    def covariance(self, scale=True, full=False, method=None, blocks=False):
         """Posterior covariance at the current parameters (vlgba_covariance:
         undamped, conditional on the fixed parameters, single rank): dict of
         cam (na, na, m) the diagonal blocks of the camera covariance, pts
         (3, 3, n) the point covariances, full (na m, na m) if ``full``, and
-        sse, dof, sigma2 = sse / dof, fixed_rows, ms (dense inverse, point
+        sse, dof, sigma2 = sse / dof, fixed_rows, ms (camera stage, point
         kernel) and scratch_bytes.  ``scale`` multiplies the matrices by
-        sigma2.  Raises VlgbaError (-1007) when the gauge is not fixed."""
-        na, ld = self.num_a, self.num_a * self.m
-        cam = np.zeros((na, na, self.m), order="F")
-        pts = np.zeros((3, 3, self.n), order="F")
-        S = np.zeros((ld, ld), order="F") if full else None
-        info = np.zeros(8)
-        check(self._L.vlgba_covariance(self._h, int(bool(scale)), _dp(cam),
-                                       _dp(S) if full else None, _dp(pts), _dp(info)),
-              "vlgba_covariance")
-        out = dict(cam=cam, pts=pts, sse=float(info[0]), dof=float(info[1]),
-                   sigma2=float(info[2]), fixed_rows=int(info[3]),
-                   ms=(float(info[4]), float(info[5])), scratch_bytes=int(info[6]))
-        if full:
-            out["full"] = S
-        return out
+        sigma2.  ``method`` ("dense" or "selected", see
+        set_covariance_method) holds for this call only; ``full`` is the dense
+        method's (VlgbaError -1001 with "selected").  ``blocks`` adds the
+        co-visible blocks of the camera covariance
+        (vlgba_get_covariance_blocks): blk_jk (nb, 2) camera pairs j >= k and
+        blocks (nb, na, na) indexed [b, r, c], in reduced_system()'s order.
+        Raises VlgbaError (-1007) when the gauge is not fixed."""
+        if method is not None and method not in COV_METHODS:
+            raise ValueError(f"method must be one of {sorted(COV_METHODS)}")
+        prev = None
+        if method is not None and method != self.get_covariance_method():
+            prev = self.get_covariance_method()
+            self.set_covariance_method(method)
+        try:
+            na, ld = self.num_a, self.num_a * self.m
+            cam = np.zeros((na, na, self.m), order="F")
+            pts = np.zeros((3, 3, self.n), order="F")
+            S = np.zeros((ld, ld), order="F") if full else None
+            info = np.zeros(8)
+            check(self._L.vlgba_covariance(self._h, int(bool(scale)), _dp(cam),
+                                           _dp(S) if full else None, _dp(pts), _dp(info)),
+                  "vlgba_covariance")
+            out = dict(cam=cam, pts=pts, sse=float(info[0]), dof=float(info[1]),
+                       sigma2=float(info[2]), fixed_rows=int(info[3]),
+                       ms=(float(info[4]), float(info[5])), scratch_bytes=int(info[6]))
+            if full:
+                out["full"] = S
+            if blocks:
+                nb = self.plan_info()["blocks"]
+                jk = np.zeros(2 * nb, dtype=np.int32)
+                blk = np.zeros(na * na * nb)
+                check(self._L.vlgba_get_covariance_blocks(self._h, jk.ctypes.data_as(c_ip),
+                                                          _dp(blk)),
+                      "vlgba_get_covariance_blocks")
+                out["blk_jk"] = jk.reshape(nb, 2)
+                out["blocks"] = blk.reshape(nb, na, na).transpose(0, 2, 1)   # [b, r, c]
+            return out
+        finally:
+            if prev is not None:
+                self.set_covariance_method(prev)
 
     def sync(self):
         check(self._L.vlgba_sync(self._h), "vlgba_sync")
@@ -569,7 +615,7 @@ def _adjuster_fingerprint(K, m, n, obs_pt, obs_cam, obs_x, o, num_vis, semantics
 def bundle_euclid_obs(K, Te, w, Xe, obs_pt, obs_cam, obs_x, *varargin, num_vis=0.0, device=0,
                       rank=0, world_size=1, comm_id=None, return_stats=False,
                       semantics="mex", adjuster=None, return_covariance=False, loss="none",
-                      loss_scale=0.0, jacobian=None, **solver):
+                      loss_scale=0.0, jacobian=None, covariance_method=None, **solver):
     """bundle_euclid on a COO observation list (0-based point / camera ids).
     ``jacobian``: "fd", "analytic" or None (BundleAdjuster); a prebuilt adjuster
     must have been made in the mode asked for here (None: its own).
@@ -580,7 +626,8 @@ def bundle_euclid_obs(K, Te, w, Xe, obs_pt, obs_cam, obs_x, *varargin, num_vis=0
     made beforehand by euclid_obs_adjuster for the same problem and options
     (or a concurrent.futures.Future of one); it is used and closed here.
     ``return_covariance`` appends BundleAdjuster.covariance() at the returned
-    parameters (after the stats, when both are asked for)."""
+    parameters (after the stats, when both are asked for), by
+    ``covariance_method`` ("dense", "selected" or None: the adjuster's)."""
     K, Te, w, Xe = _F(K), _F(Te), _F(w), _F(Xe)
     m, n = w.shape[1], Xe.shape[1]
     nomex = semantics == "nomex"
@@ -612,7 +659,7 @@ def bundle_euclid_obs(K, Te, w, Xe, obs_pt, obs_cam, obs_x, *varargin, num_vis=0
         a, b = ba.get_params()
         if return_covariance:
             ba.set_params(a, b)   # a linearisation of its own at the returned point
-            cov = ba.covariance(scale=loss == "none")
+            cov = ba.covariance(scale=loss == "none", method=covariance_method)
     # Xe_(4,:): the input's (bundle_euclid.m:267) or ones (bundle_euclid_nomex.m:364)
     out = unpack(K, a, b, np.ones((1, n)) if nomex else Xe[3:4], nvk) + (err,)
     out = out + (st,) if return_stats else out
@@ -620,10 +667,11 @@ def bundle_euclid_obs(K, Te, w, Xe, obs_pt, obs_cam, obs_x, *varargin, num_vis=0
 
 
 def bundle_euclid(K, Te, w, Xe, x, *varargin, device=0, return_stats=False, semantics="mex",
-                  return_covariance=False, loss="none", loss_scale=0.0, **solver):
+                  return_covariance=False, loss="none", loss_scale=0.0, covariance_method=None,
+                  **solver):
     """[K_ Te_ w_ Xe_ error_] = bundle_euclid(K, Te, w, Xe, x, ...)  (bundle_euclid.m:1);
-    ``loss`` / ``loss_scale`` and ``jacobian="fd" | "analytic"`` (one of the
-    solver keywords) as bundle_euclid_obs."""
+    ``loss`` / ``loss_scale``, ``covariance_method`` and ``jacobian="fd" |
+    "analytic"`` (one of the solver keywords) as bundle_euclid_obs."""
     x = _F(x)
     m, n = np.shape(w)[1], x.shape[1]
     o = parse_options(m, n, varargin, x=x, nomex=semantics == "nomex")
@@ -647,18 +695,20 @@ def bundle_euclid(K, Te, w, Xe, x, *varargin, device=0, return_stats=False, sema
     return bundle_euclid_obs(K, Te, w, Xe, pt, cam, obs_x, *rest, num_vis=num_vis,
                              device=device, return_stats=return_stats, semantics=semantics,
                              return_covariance=return_covariance, loss=loss,
-                             loss_scale=loss_scale, **solver)
+                             loss_scale=loss_scale, covariance_method=covariance_method,
+                             **solver)
 
 
 def bundle_euclid_nomex(K, Te, w, Xe, x, *varargin, device=0, return_stats=False,
-                        return_covariance=False, loss="none", loss_scale=0.0, **solver):
+                        return_covariance=False, loss="none", loss_scale=0.0,
+                        covariance_method=None, **solver):
     """[K_ Te_ w_ Xe_ error_] = bundle_euclid_nomex(K, Te, w, Xe, x, ...)
     (bundle_euclid_nomex.m:1): the same LM loop with the twin's semantics --
     db from every camera parameter (:268-277), no 'fix_pivot', Xe_(4,:) = 1."""
     return bundle_euclid(K, Te, w, Xe, x, *varargin, device=device,
                          return_stats=return_stats, semantics="nomex",
                          return_covariance=return_covariance, loss=loss,
-                         loss_scale=loss_scale, **solver)
+                         loss_scale=loss_scale, covariance_method=covariance_method, **solver)
 
 
 def bundle_euclid_resect(K, Te, w, Xs, xs, *varargin, device=0, max_iter=0, max_iter2=0,

@@ -2453,6 +2453,121 @@ __global__ __launch_bounds__(256) void k_cr32_back(const int *__restrict__ elim,
     }
 }
 
+// ---------------------------------------------------------------------------
+// Selected inverse on the camera-aligned CR factors (vlgba_covariance,
+// VLGBA_COV_SELECTED): Sigma = S^-1 on the tile-tridiagonal pattern of S, by
+// the back substitution's recurrence with matrices in place of vectors.  For a
+// record (e, p, q), Li = L_e^-1, Mp = Li^T Lp_e^T, Mq = Li^T Lq_e^T:
+//     Sigma_ep = -(Mp Sigma_pp + Mq Sigma_qp)
+//     Sigma_eq = -(Mp Sigma_qp^T + Mq Sigma_qq)
+//     Sigma_ee = Li^T Li - Sigma_ep Mp^T - Sigma_eq Mq^T
+// Levels run last to first, one launch each (p and q were eliminated above e,
+// so their tiles come from earlier launches: no in-launch hand-off); one
+// workgroup per record.  sig holds three row-major 32 x 32 tiles per CR tile:
+// Sigma_ee at sig[e], Xp[e] = Sigma_ep at sig[nt + e], Xq[e] = Sigma_eq at
+// sig[2 nt + e].  Sigma_qp is the tile Xq[p] (read as Sigma_pq) or Xp[q]
+// (transposed on the way in) of the source tile src[2 x] (chol_selinv_sources;
+// src[2 x + 1] = 1: it is p's).  Every sum is an MFMA chain in a fixed order,
+// no atomics: a repeated launch gives the same bits.  Sigma_ee is stored
+// exactly symmetric (its lower triangle, mirrored).  Padding rows / columns
+// (r >= TB, or past ld) carry the identity of the padded factors and never mix
+// with real entries, as in the factorisation.
+// LDS: seven tiles (Li -> Sigma_ep, Lp -> Mp, Lq -> Mq, Sigma_pp -> Sigma_eq,
+// Sigma_qq, Sigma_pq, Li^T -> Sigma_ee), dynamic.
+// ---------------------------------------------------------------------------
+#define CR32_SELINV_LDS (sizeof(double) * 7 * T32 * LP)
+
+// row-major src[r * 32 + c] -> LDS T[c][r]
+__device__ __forceinline__ void load_rm32_t(const double *__restrict__ src, double *T)
+{
+    const int c = threadIdx.x & 31, r0 = threadIdx.x >> 5;
+    double v[4];
+#pragma unroll
+    for (int u = 0; u < 4; u++) v[u] = src[(r0 + 8 * u) * T32 + c];
+#pragma unroll
+    for (int u = 0; u < 4; u++) T[c * LP + r0 + 8 * u] = v[u];
+}
+
+// acc (one 16 x 16 block per wave, as mfma32_nt) of A B over K = 32
+__device__ __forceinline__ d4 mfma32_nn(const double *A, const double *Bn, d4 acc)
+{
+    const int w = threadIdx.x >> 6, ra = 16 * (w >> 1), cb = 16 * (w & 1);
+    acc = mfma16_nn(A, ra, 0, Bn, 0, cb, acc);
+    return mfma16_nn(A, ra, 16, Bn, 16, cb, acc);
+}
+
+__global__ __launch_bounds__(256) void k_cr32_selinv(const int *__restrict__ elim,
+                                                     const int *__restrict__ src, int nt,
+                                                     const double *__restrict__ linv,
+                                                     const double *__restrict__ crL,
+                                                     double *__restrict__ sig)
+{
+    extern __shared__ __attribute__((aligned(16))) double sm[];
+    constexpr int TS = T32 * LP;
+    double *Li = sm, *Mp = sm + TS, *Mq = sm + 2 * TS, *Spp = sm + 3 * TS, *Sqq = sm + 4 * TS,
+           *Spq = sm + 5 * TS, *See = sm + 6 * TS;
+    double *Xp = Li, *Xq = Spp;   // (after their last reads)
+    const int x = blockIdx.x;
+    const int e = elim[3 * x], p = elim[3 * x + 1], q = elim[3 * x + 2];
+    const int st = src[2 * x], sp = src[2 * x + 1];
+    const bool hp = p >= 0, hq = q >= 0;
+    const long long T2 = (long long)T32 * T32;
+    double *See_g = sig + T2 * e, *Xp_g = sig + T2 * (nt + e), *Xq_g = sig + T2 * (2LL * nt + e);
+    load_rm32(linv + T2 * e, Li);
+    load_rm32_t(linv + T2 * e, See);   // Li^T
+    if (hp) {
+        load_rm32(crL + T2 * e, Mp);   // Lp_e
+        load_rm32(sig + T2 * p, Spp);
+    }
+    if (hq) {
+        load_rm32(crL + T2 * (nt + e), Mq);   // Lq_e
+        load_rm32(sig + T2 * q, Sqq);
+    }
+    if (hp && hq && st >= 0) {   // Sigma_pq: Xq[p], or Xp[q]^T
+        if (sp)
+            load_rm32(sig + T2 * (2LL * nt + st), Spq);
+        else
+            load_rm32_t(sig + T2 * (nt + st), Spq);
+    }
+    __syncthreads();
+    const d4 z = {0.0, 0.0, 0.0, 0.0};
+    d4 aw = mfma32_tn(Li, See, z);   // W[r][c] = sum_t Li[t][r] Li[t][c]
+    d4 ap = z, aq = z;
+    if (hp) ap = mfma32_tn(Li, Mp, z);   // Mp[r][c] = sum_t Li[t][r] Lp[c][t]
+    if (hq) aq = mfma32_tn(Li, Mq, z);
+    __syncthreads();
+    if (hp) put32(Mp, ap, 1.0, false);
+    if (hq) put32(Mq, aq, 1.0, false);
+    __syncthreads();
+    // Sigma_ep = -(Mp Sigma_pp + Mq Sigma_pq^T), Sigma_eq = -(Mp Sigma_pq + Mq Sigma_qq)
+    // (Sigma_pp, Sigma_qq are exactly symmetric: the nt form reads them as stored)
+    ap = aq = z;
+    if (hp) ap = mfma32_nt(Mp, Spp, ap);
+    if (hp && hq) ap = mfma32_nt(Mq, Spq, ap);
+    if (hp && hq) aq = mfma32_nn(Mp, Spq, aq);
+    if (hq) aq = mfma32_nt(Mq, Sqq, aq);
+    __syncthreads();
+    if (hp) put32(Xp, ap, -1.0, false);
+    if (hq) put32(Xq, aq, -1.0, false);
+    __syncthreads();
+    // Sigma_ee = W - Sigma_ep Mp^T - Sigma_eq Mq^T
+    d4 as = z;
+    if (hp) as = mfma32_nt(Xp, Mp, as);
+    if (hq) as = mfma32_nt(Xq, Mq, as);
+    put32(See, aw - as, 1.0, false);
+    __syncthreads();
+    {
+        const int c = threadIdx.x & 31, r0 = threadIdx.x >> 5;
+#pragma unroll
+        for (int u = 0; u < 4; u++) {
+            const int r = r0 + 8 * u;
+            See_g[r * T32 + c] = r >= c ? See[r * LP + c] : See[c * LP + r];
+        }
+    }
+    if (hp) store_rm32(Xp_g, Xp);
+    if (hq) store_rm32(Xq_g, Xq);
+}
+
 // One record of the one-launch back substitution: it loads its three tiles,
 // forms z, Mp and Mq (cr32_back_core), then waits for x_p and x_q, which the
 // records of the tiles eliminated above it publish as epoch-tagged 8-byte
@@ -3378,13 +3493,75 @@ static int envelope_backward(ba_dev *d, long long L, double *x, int nospin)
     return -(int)hipGetLastError();
 }
 
+// The factor half of the camera-aligned CR, one launch per level: L_e^-1 into
+// linv, the panels into crL, y into ywork, the pivot status into scal[4]
+// (ba_chol_solve's per-level path, and the selected inverse of
+// vlgba_covariance, which runs no back substitution after it)
+int ba_cr32_factor(ba_dev *d)
+{
+    const std::vector<int> &eptr = d->plan->eptr;
+    const std::vector<int> &fptr = d->plan->fptr, &sptr = d->plan->sptr;
+    const int ncu32 = d->ncu;
+    const int n32 = d->nt32, TB = d->tb32;
+    {   // level 0 on the assembled S
+        const int ne = eptr[1];
+        const int fs = 3 * ne <= 2 * ncu32;   // ~60 KB LDS: two workgroups per CU
+        KT_B(d);
+        k_cr32_factor<<<fs ? 3 * ne : ne, 256, 0, d->stream>>>(
+            d->S, d->lds, TB, d->ld, d->cr_elim, n32, d->linv, d->crL, d->rhs, d->ywork,
+            d->scal + 4, fs);
+        KT_E(d, KT_CR_FACTOR);
+    }
+    // levels >= 1: the previous level's update folded into the factor launch
+    for (int l = 1; l < d->cr_nlev; l++) {
+        const int f0 = fptr[l], ne = fptr[l + 1] - f0;
+        const int s0 = sptr[l], ns = sptr[l + 1] - s0;
+        KT_B(d);
+        k_cr32_level<<<3 * ne + ns, 256, 0, d->stream>>>(
+            d->S, d->lds, TB, d->ld, d->crf + 5 * f0, ne, d->crs + 3 * s0, n32, d->linv,
+            d->crL, d->rhs, d->ywork, d->scal + 4);
+        KT_E(d, KT_CR_FACTOR);
+    }
+    return -(int)hipGetLastError();
+}
+
+// The selected inverse's descent on the factors ba_cr32_factor left: levels
+// last to first, one launch each.  sig: [3][nt32][32 * 32] doubles; src: device
+// [2 * records] (chol_selinv_sources, the source record replaced by its tile)
+int ba_cr32_selinv(ba_dev *d, const int *src, double *sig)
+{
+    const std::vector<int> &eptr = d->plan->eptr;
+    TRY_RC(ba_ensure_dyn_lds((const void *)k_cr32_selinv, CR32_SELINV_LDS));
+    for (int l = d->cr_nlev - 1; l >= 0; l--) {
+        const int e0 = eptr[l], ne = eptr[l + 1] - e0;
+        k_cr32_selinv<<<ne, 256, CR32_SELINV_LDS, d->stream>>>(
+            d->cr_elim + 3 * e0, src + 2 * e0, d->nt32, d->linv, d->crL, sig);
+    }
+    return -(int)hipGetLastError();
+}
+
+// host: per elimination record the tile holding Sigma_qp (-1: none) and whether
+// it is p's, for ba_cr32_selinv: src [2 * nt32] (one record per tile)
+int ba_cr32_selinv_sources(const ba_dev *d, int *src)
+{
+    if (!d->plan || !(d->cr_nlev > 0 && d->cr32)) return -1000;
+    const std::vector<int> &elim = d->plan->elim;
+    std::vector<int> s;
+    if (chol_selinv_sources(elim, d->plan->eptr, s) || s.size() != 2 * (size_t)d->nt32)
+        return -1000;
+    for (size_t i = 0; i < s.size(); i += 2) {
+        src[i] = s[i] >= 0 ? elim[3 * (size_t)s[i]] : -1;
+        src[i + 1] = s[i + 1];
+    }
+    return 0;
+}
+
 int ba_chol_solve(ba_dev *d, int nospin)
 {
     const int nt = d->nt;
     d->camupd_done = 0;   // only the one-launch CR below does the camera update
     const size_t smem3 = sizeof(double) * 3 * NB * LP;
     const std::vector<int> &eptr = d->plan->eptr, &kptr = d->plan->kptr;
-    const std::vector<int> &fptr = d->plan->fptr, &sptr = d->plan->sptr;
     TRY_RC(ba_ensure_dyn_lds((const void *)k_factor_step, smem3));
     TRY_RC(ba_ensure_dyn_lds((const void *)k_cr_factor, smem3));
     TRY_RC(ba_ensure_dyn_lds((const void *)k_cr_update, smem3));
@@ -3419,27 +3596,8 @@ int ba_chol_solve(ba_dev *d, int nospin)
         return -(int)hipGetLastError();
     }
     if (d->cr_nlev > 0 && d->cr32) {   // camera-aligned 32-row tiles
-        const int ncu32 = d->ncu;
         const int n32 = d->nt32, TB = d->tb32;
-        {   // level 0 on the assembled S
-            const int ne = eptr[1];
-            const int fs = 3 * ne <= 2 * ncu32;   // ~60 KB LDS: two workgroups per CU
-            KT_B(d);
-            k_cr32_factor<<<fs ? 3 * ne : ne, 256, 0, d->stream>>>(
-                d->S, d->lds, TB, d->ld, d->cr_elim, n32, d->linv, d->crL, d->rhs, d->ywork,
-                d->scal + 4, fs);
-            KT_E(d, KT_CR_FACTOR);
-        }
-        // levels >= 1: the previous level's update folded into the factor launch
-        for (int l = 1; l < d->cr_nlev; l++) {
-            const int f0 = fptr[l], ne = fptr[l + 1] - f0;
-            const int s0 = sptr[l], ns = sptr[l + 1] - s0;
-            KT_B(d);
-            k_cr32_level<<<3 * ne + ns, 256, 0, d->stream>>>(
-                d->S, d->lds, TB, d->ld, d->crf + 5 * f0, ne, d->crs + 3 * s0, n32, d->linv,
-                d->crL, d->rhs, d->ywork, d->scal + 4);
-            KT_E(d, KT_CR_FACTOR);
-        }
+        TRY_RC(ba_cr32_factor(d));
         const int nrec = eptr[d->cr_nlev];
         if (d->xgran && nrec <= 2 * d->ncu && !nospin) {   // every record co-resident: one launch
             if (++d->back_epoch == 0) d->back_epoch = 1;

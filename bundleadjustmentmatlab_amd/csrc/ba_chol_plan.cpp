@@ -117,6 +117,39 @@ void cr32_fplan_build(const chol_plan &p, int ncu, cr32_fplan &P)
     P.sofs[nl] = p.sptr[nl];
     for (int l = 0; l <= nl; l++) P.eofs[l] = p.eptr[l];
 }
+// the cyclic reduction's records for nt tiles: per level the even positions of
+// the active list are eliminated (e, p, q: the kept neighbours, -1 at the ends)
+// and the odd ones kept (k, e-, e+, k2: the next kept tile)
+void cr_records(int nt, std::vector<int> &elim, std::vector<int> &keep, std::vector<int> &eptr,
+                std::vector<int> &kptr)
+{
+    std::vector<int> act(nt);
+    elim.clear();
+    keep.clear();
+    eptr.assign(1, 0);
+    kptr.assign(1, 0);
+    for (int i = 0; i < nt; i++) act[i] = i;
+    while (!act.empty()) {
+        const int len = (int)act.size();
+        std::vector<int> next;
+        for (int t = 0; t < len; t++) {
+            if ((t & 1) == 0) {
+                elim.push_back(act[t]);
+                elim.push_back(t > 0 ? act[t - 1] : -1);
+                elim.push_back(t + 1 < len ? act[t + 1] : -1);
+            } else {
+                keep.push_back(act[t]);
+                keep.push_back(act[t - 1]);
+                keep.push_back(t + 1 < len ? act[t + 1] : -1);
+                keep.push_back(t + 2 < len ? act[t + 2] : -1);
+                next.push_back(act[t]);
+            }
+        }
+        eptr.push_back((int)elim.size() / 3);
+        kptr.push_back((int)keep.size() / 4);
+        act.swap(next);
+    }
+}
 }   // namespace
 
 #pragma GCC visibility pop
@@ -129,6 +162,55 @@ vlgba_debug_nd_plan(int m, int num_a, const int *blk_jk, int nb, int *bnd, int *
         if (blk_jk[2 * b] < blk_jk[2 * b + 1] || blk_jk[2 * b + 1] < 0 || blk_jk[2 * b] >= m)
             return -1;
     return nd_choose(nd_min_cam(m, blk_jk, nb), m, num_a, bnd, *crit);
+}
+
+#pragma GCC visibility push(hidden)
+
+int chol_selinv_sources(const std::vector<int> &elim, const std::vector<int> &eptr,
+                        std::vector<int> &src)
+{
+    const int nrec = (int)elim.size() / 3, nlev = (int)eptr.size() - 1;
+    src.assign(2 * (size_t)nrec, 0);
+    if (nlev < 0 || (nrec > 0 && (nlev < 1 || eptr[nlev] != nrec))) return -1;
+    int nt = 0;
+    for (int i = 0; i < nrec; i++) nt = std::max(nt, elim[3 * i] + 1);
+    std::vector<int> rec_of(nt, -1), lev_of(nt, -1);
+    for (int l = 0; l < nlev; l++)
+        for (int i = eptr[l]; i < eptr[l + 1]; i++) {
+            const int e = elim[3 * i];
+            if (e < 0 || rec_of[e] >= 0) return -1;
+            rec_of[e] = i;
+            lev_of[e] = l;
+        }
+    for (int i = 0; i < nrec; i++) {
+        const int e = elim[3 * i], p = elim[3 * i + 1], q = elim[3 * i + 2];
+        src[2 * (size_t)i] = -1;
+        if (p < 0 || q < 0) continue;
+        if (p >= nt || q >= nt || rec_of[p] < 0 || rec_of[q] < 0) return -1;
+        if (lev_of[p] <= lev_of[e] || lev_of[q] <= lev_of[e] || lev_of[p] == lev_of[q]) return -1;
+        const bool first_p = lev_of[p] < lev_of[q];
+        const int s = first_p ? rec_of[p] : rec_of[q];
+        // the other tile is the source's neighbour on that side
+        if (first_p ? elim[3 * s + 2] != q : elim[3 * s + 1] != p) return -1;
+        src[2 * (size_t)i] = s;
+        src[2 * (size_t)i + 1] = first_p ? 1 : 0;
+    }
+    return 0;
+}
+
+#pragma GCC visibility pop
+
+extern "C" __attribute__((visibility("default"))) int
+vlgba_debug_selinv_plan(int ntiles, int *elim, int *eptr, int *src)
+{
+    if (ntiles < 1 || !elim || !eptr || !src) return -1;
+    std::vector<int> el, keep, ep, kp, sr;
+    cr_records(ntiles, el, keep, ep, kp);
+    if ((int)el.size() != 3 * ntiles || chol_selinv_sources(el, ep, sr)) return -1;
+    std::copy(el.begin(), el.end(), elim);
+    std::copy(ep.begin(), ep.end(), eptr);
+    std::copy(sr.begin(), sr.end(), src);
+    return (int)ep.size() - 1;
 }
 
 #pragma GCC visibility push(hidden)
@@ -192,31 +274,8 @@ int chol_plan_build(const chol_plan_in &in, chol_plan &out)
     if (out.cr32) tridiag = true;
     if (tridiag) {
         const int nt = ntc;   // the CR tile count (64- or camera-aligned 32-row tiles)
-        std::vector<int> act(nt), &elim = out.elim, &keep = out.keep, &eptr = out.eptr,
-                                  &kptr = out.kptr;
-        eptr.assign(1, 0);
-        kptr.assign(1, 0);
-        for (int i = 0; i < nt; i++) act[i] = i;
-        while (!act.empty()) {
-            const int len = (int)act.size();
-            std::vector<int> next;
-            for (int t = 0; t < len; t++) {
-                if ((t & 1) == 0) {
-                    elim.push_back(act[t]);
-                    elim.push_back(t > 0 ? act[t - 1] : -1);
-                    elim.push_back(t + 1 < len ? act[t + 1] : -1);
-                } else {
-                    keep.push_back(act[t]);
-                    keep.push_back(act[t - 1]);
-                    keep.push_back(t + 1 < len ? act[t + 1] : -1);
-                    keep.push_back(t + 2 < len ? act[t + 2] : -1);
-                    next.push_back(act[t]);
-                }
-            }
-            eptr.push_back((int)elim.size() / 3);
-            kptr.push_back((int)keep.size() / 4);
-            act.swap(next);
-        }
+        std::vector<int> &elim = out.elim, &keep = out.keep, &eptr = out.eptr, &kptr = out.kptr;
+        cr_records(nt, elim, keep, eptr, kptr);
         out.cr_nlev = (int)eptr.size() - 1;
         {   // the CR's algorithmic flops (ba_dev::fl_factor): per elimination
             // record (e, p, q) the factor + inverse of D_e, y_e and one panel per

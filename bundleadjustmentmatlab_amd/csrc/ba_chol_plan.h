@@ -107,6 +107,16 @@ struct chol_plan {
 
 // A function of its arguments only.  Returns 0.
 int chol_plan_build(const chol_plan_in &in, chol_plan &out);
+// The selected inverse on the CR factors (k_cr32_selinv, ba_chol.hip) walks the
+// elimination records back down; record i = (e, p, q) with both neighbours
+// needs Sigma_qp, which the record of whichever of p, q was eliminated first
+// (the lower level above e's) holds, since the other is its neighbour there:
+// src[2 i] = that record, src[2 i + 1] = 1 when it is p's (Sigma_qp = Xq[p]^T),
+// 0 when it is q's (Sigma_qp = Xp[q]); src[2 i] = -1 where p or q is absent.
+// A function of elim / eptr alone.  Returns 0, or -1 for lists that are not a
+// cyclic reduction's (a neighbour never eliminated, or not the source's).
+int chol_selinv_sources(const std::vector<int> &elim, const std::vector<int> &eptr,
+                        std::vector<int> &src);
 // Step st of the ND arcs' side-by-side factorization (run: the runner started)
 void chol_nd_step(const chol_plan &plan, int st, bool run, nd_step *P);
 

@@ -7,6 +7,12 @@
 //   Sigma_b_i = V+_i + V+_i T_i V+_i,
 //   T_i       = sum_{j,k in cams(i)} W_ij^T Sigma_a[j,k] W_ik      (k_point_cov)
 //
+// The selected method (VLGBA_COV_SELECTED) forms Sigma_a only on the co-visible
+// pattern, in the tiles of the cyclic reduction's selected inverse
+// (k_cr32_selinv, ba_chol.hip); here are its fixed-row mask from the blocks
+// (k_cov_mark_fixed_blocks) and the extraction of the diagonal and packed
+// co-visible blocks from those tiles (k_cov_extract).  k_point_cov is the same.
+//
 // k_point_cov is one streaming pass over the observations, point-major like
 // the Schur kernels: a point's W rows (NA x 3 each) are staged in LDS once and
 // read by every camera pair of its track.  Sigma_a[k,j] = Sigma_a[j,k]^T, so
@@ -248,6 +254,77 @@ __global__ void k_cov_pack(const double *__restrict__ S, long long ld, int na,
     if (q >= nn * nb) return;
     const long long p = q / nn, e = q % nn, r = e % na, c = e / na;
     packed[q] = S[((long long)na * bj[p] + r) + ld * ((long long)na * bk[p] + c)];
+}
+
+// ---- the selected method (VLGBA_COV_SELECTED): Sigma_a on the tile-tridiagonal
+// pattern of S0, in the tiles of the CR's selected inverse (k_cr32_selinv,
+// ba_chol.hip) ----
+// the fixed rows from the co-visible blocks (fixed preset to 1: a camera
+// without a diagonal block has an all-zero row)
+__global__ void k_cov_mark_fixed_blocks(const int *__restrict__ blk_jk,
+                                        const double *__restrict__ sblk, int nb, int na,
+                                        unsigned char *__restrict__ fixed)
+{
+    const long long q = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (q >= (long long)nb * na) return;
+    const long long p = q / na;
+    const int r = (int)(q % na), j = blk_jk[2 * p];
+    if (j != blk_jk[2 * p + 1]) return;
+    fixed[(long long)na * j + r] = sblk[(long long)na * na * p + r + na * r] == 0.0 ? 1 : 0;
+}
+
+// Entry q < na^2 nb: entry (r, c) of packed block p = (bj[p], bk[p]), bj >= bk;
+// then na^2 m more: the diagonal blocks.  Camera j lives in tile j / G at rows
+// na (j % G) (G = TB / na cameras a tile).  Same tile: Sigma_ee of the tile;
+// adjacent tiles (tj = tk + 1): the even one was eliminated at level 0 with the
+// other as its neighbour -- Xp[tj] = Sigma(tj, tk) as stored, or Xq[tk] =
+// Sigma(tk, tj) transposed.  Rows r >= TB of a tile (padding) are never read.
+__global__ void k_cov_extract(const double *__restrict__ sig, int nt, int TB, int na, int m,
+                              const unsigned char *__restrict__ fixed,
+                              const int *__restrict__ bj, const int *__restrict__ bk, int nb,
+                              double *__restrict__ diag, double *__restrict__ packed)
+{
+    const long long q = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    const long long nn = (long long)na * na;
+    if (q >= nn * ((long long)nb + m)) return;
+    const bool dg = q >= nn * nb;
+    const long long p = dg ? (q - nn * nb) / nn : q / nn;
+    const int e = (int)(q % nn), r = e % na, c = e / na;
+    const int j = dg ? (int)p : bj[p], k = dg ? (int)p : bk[p];
+    const int G = TB / na, tj = j / G, tk = k / G;
+    const int rj = na * (j % G) + r, ck = na * (k % G) + c;
+    const long long T2 = 32 * 32;
+    double v = 0.0;
+    if (!(fixed[(long long)na * j + r] || fixed[(long long)na * k + c])) {
+        if (tj == tk)
+            v = sig[T2 * tj + 32 * rj + ck];
+        else if (tk & 1)   // tj is even: Xp[tj]
+            v = sig[T2 * ((long long)nt + tj) + 32 * rj + ck];
+        else               // tk is even: Xq[tk]^T
+            v = sig[T2 * (2LL * nt + tk) + 32 * ck + rj];
+    }
+    (dg ? diag : packed)[dg ? q - nn * nb : q] = v;
+}
+
+int ba_cov_mark_fixed_blocks(ba_dev *d, unsigned char *fixed)
+{
+    if (d->ld <= 0) return 0;
+    VLGBA_CHECK(hipMemsetAsync(fixed, 1, (size_t)d->ld, d->stream));
+    const long long q = (long long)d->nb * d->na;
+    if (q > 0)
+        k_cov_mark_fixed_blocks<<<(int)((q + 255) / 256), 256, 0, d->stream>>>(
+            d->blk_jk, d->sblk, d->nb, d->na, fixed);
+    return -(int)hipGetLastError();
+}
+
+int ba_cov_extract(ba_dev *d, const double *sig, const unsigned char *fixed, const int *bj,
+                   const int *bk, int nb, double *diag, double *packed)
+{
+    const long long q = (long long)d->na * d->na * ((long long)nb + d->m);
+    if (q > 0)
+        k_cov_extract<<<(int)((q + 255) / 256), 256, 0, d->stream>>>(
+            sig, d->nt32, d->tb32, d->na, d->m, fixed, bj, bk, nb, diag, packed);
+    return -(int)hipGetLastError();
 }
 
 int ba_cov_pack(ba_dev *d, const double *S, long long ld, const int *bj, const int *bk, int nb,

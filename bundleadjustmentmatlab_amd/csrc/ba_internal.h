@@ -377,6 +377,14 @@ int ba_chol_fix_diag(ba_dev *d);
 // nospin = 1: only launches that never wait on other workgroups (the
 // per-level / per-column paths) -- the re-solve after a hand-off timeout
 int ba_chol_solve(ba_dev *d, int nospin = 0);
+// camera-aligned CR (cr32) only: the factor launches of the per-level path
+// alone (no back substitution, da and camupd_done untouched); the selected
+// inverse's tile sources on the host (src [2 * nt32]: tile holding Sigma_qp or
+// -1, 1 when it is p's) and its descent on the device (src uploaded, sig
+// [3][nt32][32 * 32]: Sigma_ee | Sigma_ep | Sigma_eq, row major)
+int ba_cr32_factor(ba_dev *d);
+int ba_cr32_selinv_sources(const ba_dev *d, int *src);
+int ba_cr32_selinv(ba_dev *d, const int *src, double *sig);
 // da = pinv(S) rhs from the eigen-decomposition S = V diag(ev) V^T (ev
 // ascending, V column major ld x ld): MATLAB's tolerance ld * eps(max |ev|)
 int ba_pinv_apply(ba_dev *d, const double *V, const double *ev, long long ld, const double *rhs,
@@ -408,6 +416,14 @@ struct ba_cov_src {
 // packed[p] = block (bj[p], bk[p]) of the dense S, p < nb
 int ba_cov_pack(ba_dev *d, const double *S, long long ld, const int *bj, const int *bk, int nb,
                 double *packed);
+// the selected method: fixed[r] = 1 where the diagonal entry of row r in the
+// co-visible blocks sblk is exactly zero or no diagonal block covers it (the
+// rows ba_cov_mark_fixed finds in the dense S0 assembled from the same blocks)
+int ba_cov_mark_fixed_blocks(ba_dev *d, unsigned char *fixed);
+// ... and diag (na x na x m) and packed (block p = (bj[p], bk[p]), p < nb) from
+// the selected inverse's tiles sig (ba_cr32_selinv), fixed rows / columns zero
+int ba_cov_extract(ba_dev *d, const double *sig, const unsigned char *fixed, const int *bj,
+                   const int *bk, int nb, double *diag, double *packed);
 // Sigma_b of the points list[0 .. n8 + n64 + nwg) (internal order, binned by
 // track length as above; tmax: the longest track) into out [n][9]; reads d->W
 // and d->Vinv (lambda = 0)

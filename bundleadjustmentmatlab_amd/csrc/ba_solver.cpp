@@ -258,9 +258,21 @@ struct vlgba_ctx {
     double *cov_diag = nullptr, *cov_pts = nullptr;
     // ... and the packed copy of Sigma_a's co-visible blocks k_point_cov reads
     // (CSR by camera row: cov_rowptr [m + 1], cov_col / cov_bj [nb];
-    // VLGBA_COV_PACKED=0: none, the kernel reads the dense inverse -- A/B)
+    // VLGBA_COV_PACKED=0: the dense method's kernel reads the dense inverse -- A/B)
     int *cov_rowptr = nullptr, *cov_col = nullptr, *cov_bj = nullptr;
     double *cov_packed = nullptr;
+    int cov_src_packed = 1;       // k_point_cov of the dense method reads the packed copy
+    std::vector<int> cov_ord;     // packed block p is block cov_ord[p] of blk_jk
+    // the last successful call's blocks are in cov_packed (times cov_scale:
+    // vlgba_get_covariance_blocks)
+    int cov_have = 0;
+    double cov_scale = 1.0;
+    // VLGBA_COV_SELECTED (vlgba_set_covariance_method): the selected inverse on
+    // the camera-aligned CR factors -- its tile sources and three 32 x 32 tiles
+    // per CR tile (allocated on the method's first call)
+    int cov_method = VLGBA_COV_DENSE;
+    int *cov_selsrc = nullptr;
+    double *cov_sig = nullptr;
 };
 
 // Per-device pool of the context's streams, fork/join events and host-mapped
@@ -1695,13 +1707,18 @@ static int cov_setup(vlgba_ctx *c)
     TRY(ctx_alloc(c, &c->cov_list, std::max<size_t>(1, list.size())));
     TRY(upload(c->cov_list, list.data(), list.size(), d.stream));
     VLGBA_CHECK(hipStreamSynchronize(d.stream));   // list goes out of scope
+    // VLGBA_COV_PACKED=0: the dense method's k_point_cov reads the dense inverse
+    // (A/B); the packed copy is still filled, after the point kernel, for
+    // vlgba_get_covariance_blocks
     const char *pk = std::getenv("VLGBA_COV_PACKED");
-    if (!(pk && pk[0] == '0')) {
+    c->cov_src_packed = !(pk && pk[0] == '0');
+    {
         // the co-visible blocks (j >= k) by camera row j, columns ascending
         std::vector<int> jk(2 * (size_t)d.nb);
         TRY(download(jk.data(), d.blk_jk, jk.size(), d.stream));
         VLGBA_CHECK(hipStreamSynchronize(d.stream));
-        std::vector<int> ord((size_t)d.nb);
+        std::vector<int> &ord = c->cov_ord;
+        ord.resize((size_t)d.nb);
         std::iota(ord.begin(), ord.end(), 0);
         std::sort(ord.begin(), ord.end(), [&](int x, int y) {
             return jk[2 * (size_t)x] != jk[2 * (size_t)y] ? jk[2 * (size_t)x] < jk[2 * (size_t)y]
@@ -1738,15 +1755,38 @@ static int cov_setup(vlgba_ctx *c)
     return 0;
 }
 
+// ... and of the selected method: the tile sources of its descent and its tiles
+static int cov_setup_selected(vlgba_ctx *c)
+{
+    ba_dev &d = c->d;
+    if (c->cov_sig) return 0;
+    std::vector<int> src(2 * (size_t)d.nt32);
+    TRY(ba_cr32_selinv_sources(&d, src.data()));
+    TRY(ctx_alloc(c, &c->cov_selsrc, src.size()));
+    TRY(upload(c->cov_selsrc, src.data(), src.size(), d.stream));
+    VLGBA_CHECK(hipStreamSynchronize(d.stream));   // src goes out of scope
+    const size_t cnt = (size_t)3 * 32 * 32 * d.nt32;
+    double *sig = nullptr;
+    TRY(ctx_alloc(c, &sig, cnt));
+    VLGBA_CHECK(hipMemsetAsync(sig, 0, sizeof(double) * cnt, d.stream));
+    c->cov_sig = sig;
+    return 0;
+}
+
 static int cov_run(vlgba_ctx *c, int scale, double *cov_a, double *cov_a_full, double *cov_b,
                    double *info)
 {
     ba_dev &d = c->d;
+    const bool sel = c->cov_method == VLGBA_COV_SELECTED;
     rs_api *rs = nullptr;
     rocblas_handle hdl = nullptr;
-    TRY(rs_prepare(c, &rs, &hdl));
-    if (!rs->potrf || !rs->potri) return VLGBA_E_ARG;
+    if (!sel) {   // (the selected method needs neither rocSOLVER nor the dense scratch)
+        TRY(rs_prepare(c, &rs, &hdl));
+        if (!rs->potrf || !rs->potri) return VLGBA_E_ARG;
+    }
     TRY(cov_setup(c));
+    if (sel) TRY(cov_setup_selected(c));
+    c->cov_have = 0;
     const long long ld = d.ld;
     // stage 1 at the current parameters, as a pass would run it
     if (!c->lin_valid || c->camred_due) {
@@ -1761,6 +1801,33 @@ static int cov_run(vlgba_ctx *c, int scale, double *cov_a, double *cov_a_full, d
     }
     hipEvent_t ev[3] = {};
     for (auto &e : ev) VLGBA_CHECK(hipEventCreate(&e));
+    // the selected method: S0 in the CR's tiles as a pass assembles it (unit
+    // diagonal on the exactly-zero rows), the fixed rows from the blocks, the
+    // per-level factor launches, the descent, and the co-visible blocks out of
+    // its tiles; no back substitution, da and the dense scratch untouched
+    auto run_selected = [&]() -> int {
+        VLGBA_CHECK(hipEventRecord(ev[0], d.stream));
+        TRY(schur_phase(c, 0.0));
+        if (d.join_pending) {
+            VLGBA_CHECK(hipStreamWaitEvent(d.stream, d.ev_join, 0));
+            d.join_pending = 0;
+        }
+        TRY(ba_launch_assemble(&d));
+        TRY(ba_cov_mark_fixed_blocks(&d, c->cov_fixed));
+        TRY(ba_cr32_factor(&d));
+        TRY(ba_cr32_selinv(&d, c->cov_selsrc, c->cov_sig));
+        TRY(ba_cov_extract(&d, c->cov_sig, c->cov_fixed, c->cov_bj, c->cov_col, d.nb,
+                           c->cov_diag, c->cov_packed));
+        VLGBA_CHECK(hipEventRecord(ev[1], d.stream));
+        const ba_cov_src src{nullptr, ld, c->cov_rowptr, c->cov_col, c->cov_packed};
+        TRY(ba_launch_point_cov(&d, c->cov_list, c->cov_n8, c->cov_n64, c->cov_nwg, c->cov_tmax,
+                                &src, c->cov_pts));
+        VLGBA_CHECK(hipEventRecord(ev[2], d.stream));
+        double pivot = 0.0;   // the CR's status word: a non-positive pivot
+        TRY(download(&pivot, d.scal + 4, 1, d.stream));
+        VLGBA_CHECK(hipStreamSynchronize(d.stream));
+        return pivot != 0.0 ? VLGBA_E_SINGULAR : 0;
+    };
     auto run = [&]() -> int {
         VLGBA_CHECK(hipEventRecord(ev[0], d.stream));
         // S0: the undamped Schur phase (it also leaves V+ = vlg_pinv3(V) in d.Vinv),
@@ -1795,17 +1862,20 @@ static int cov_run(vlgba_ctx *c, int scale, double *cov_a, double *cov_a_full, d
             if (pinfo != 0) return VLGBA_E_SINGULAR;
         }
         TRY(ba_cov_finish(&d, c->pinv_S, ld, c->cov_fixed, c->cov_diag));
-        if (c->cov_packed)
+        if (c->cov_src_packed)
             TRY(ba_cov_pack(&d, c->pinv_S, ld, c->cov_bj, c->cov_col, d.nb, c->cov_packed));
         VLGBA_CHECK(hipEventRecord(ev[1], d.stream));
-        const ba_cov_src src{c->pinv_S, ld, c->cov_rowptr, c->cov_col, c->cov_packed};
+        const ba_cov_src src{c->pinv_S, ld, c->cov_rowptr, c->cov_col,
+                             c->cov_src_packed ? c->cov_packed : nullptr};
         TRY(ba_launch_point_cov(&d, c->cov_list, c->cov_n8, c->cov_n64, c->cov_nwg, c->cov_tmax,
                                 &src, c->cov_pts));
         VLGBA_CHECK(hipEventRecord(ev[2], d.stream));
+        if (!c->cov_src_packed)   // (for vlgba_get_covariance_blocks only)
+            TRY(ba_cov_pack(&d, c->pinv_S, ld, c->cov_bj, c->cov_col, d.nb, c->cov_packed));
         VLGBA_CHECK(hipStreamSynchronize(d.stream));
         return 0;
     };
-    int rc = run();
+    int rc = sel ? run_selected() : run();
     float ms_a = 0.f, ms_b = 0.f;
     if (!rc) {
         (void)hipEventElapsedTime(&ms_a, ev[0], ev[1]);
@@ -1827,8 +1897,9 @@ static int cov_run(vlgba_ctx *c, int scale, double *cov_a, double *cov_a_full, d
                        ((double)(ld - nfixed) + (c->flags.fix_structure ? 0.0 : 3.0 * c->cov_seen));
     const double sigma2 = dof > 0 ? sse / dof : 0.0;
     if (info) {
-        const double v[8] = {sse, dof, sigma2, (double)nfixed, ms_a, ms_b,
-                             8.0 * (double)ld * (double)ld, 0.0};
+        const double scratch = sel ? 8.0 * 3.0 * 32.0 * 32.0 * (double)d.nt32
+                                   : 8.0 * (double)ld * (double)ld;
+        const double v[8] = {sse, dof, sigma2, (double)nfixed, ms_a, ms_b, scratch, 0.0};
         std::memcpy(info, v, sizeof v);
     }
     if (scale && !(dof > 0)) return VLGBA_E_ARG;
@@ -1837,6 +1908,8 @@ static int cov_run(vlgba_ctx *c, int scale, double *cov_a, double *cov_a_full, d
     if (cov_a_full) TRY(download(cov_a_full, c->pinv_S, (size_t)(ld * ld), d.stream));
     if (cov_b) TRY(download_points(c, cov_b, c->cov_pts, 9));
     VLGBA_CHECK(hipStreamSynchronize(d.stream));
+    c->cov_have = 1;
+    c->cov_scale = scale ? sigma2 : 1.0;
     if (scale) {
         for (size_t q = 0; cov_a && q < na2m; q++) cov_a[q] *= sigma2;
         for (size_t q = 0; cov_a_full && q < (size_t)(ld * ld); q++) cov_a_full[q] *= sigma2;
@@ -1854,6 +1927,8 @@ int vlgba_covariance(vlgba_ctx *c, int scale, double *cov_a, double *cov_a_full,
     if (c->world > 1 || c->comm || c->host_allreduce) return VLGBA_E_ARG;
     // sigma2 from a robust cost is not the noise variance: unscaled only
     if (scale && c->d.loss_kind) return VLGBA_E_ARG;
+    // the full matrix is the dense method's
+    if (cov_a_full && c->cov_method == VLGBA_COV_SELECTED) return VLGBA_E_ARG;
     TRY(ctx_enter(c));
     // the call's launches stay out of the pass timers
     const int timing = c->timing;
@@ -1864,6 +1939,46 @@ int vlgba_covariance(vlgba_ctx *c, int scale, double *cov_a, double *cov_a_full,
     c->timing = timing;
     if (c->d.kt) c->d.kt->on = kt_on;
     return rc;
+}
+
+// the selected method runs on the camera-aligned cyclic reduction's factors
+static bool cov_selected_ok(const vlgba_ctx *c)
+{
+    return c->d.cr_nlev > 0 && c->d.cr32 && c->world == 1 && !c->comm && !c->host_allreduce &&
+           !c->d.ordered;
+}
+
+int vlgba_set_covariance_method(vlgba_ctx *c, int kind)
+{
+    if (!c || (kind != VLGBA_COV_DENSE && kind != VLGBA_COV_SELECTED)) return VLGBA_E_ARG;
+    if (kind == VLGBA_COV_SELECTED && !cov_selected_ok(c)) return VLGBA_E_ARG;
+    c->cov_method = kind;
+    return 0;
+}
+
+int vlgba_get_covariance_method(vlgba_ctx *c, int *kind)
+{
+    if (!c || !kind) return VLGBA_E_ARG;
+    *kind = c->cov_method;
+    return 0;
+}
+
+int vlgba_get_covariance_blocks(vlgba_ctx *c, int *blk_jk, double *blocks)
+{
+    if (!c || !c->cov_have || !c->cov_packed) return VLGBA_E_ARG;
+    TRY(ctx_enter(c));
+    ba_dev &d = c->d;
+    const size_t nn = (size_t)d.na * d.na;
+    if (blk_jk) TRY(download(blk_jk, d.blk_jk, 2 * (size_t)d.nb, d.stream));
+    std::vector<double> pk(blocks ? nn * d.nb : 0);
+    if (blocks) TRY(download(pk.data(), c->cov_packed, pk.size(), d.stream));
+    VLGBA_CHECK(hipStreamSynchronize(d.stream));
+    // packed block p (by camera row, columns ascending) is block cov_ord[p]
+    for (int p = 0; blocks && p < d.nb; p++) {
+        double *o = blocks + nn * (size_t)c->cov_ord[p];
+        for (size_t q = 0; q < nn; q++) o[q] = pk[nn * p + q] * c->cov_scale;
+    }
+    return 0;
 }
 
 int vlgba_set_loss(vlgba_ctx *c, int kind, double scale)

@@ -75,7 +75,7 @@ def unpack(a, b, Xp4):
 def bundle_projective_obs(Pp, Xp, obs_pt, obs_cam, obs_x, *varargin, num_vis=0.0, device=0,
                           rank=0, world_size=1, comm_id=None, return_stats=False,
                           semantics="mex", return_covariance=False, loss="none",
-                          loss_scale=0.0, **solver_kw):
+                          loss_scale=0.0, covariance_method=None, **solver_kw):
     """bundle_projective on a COO observation list (0-based point / camera ids);
     varargin takes 'fix_structure', 'fix_motion', 'verbose' (visibility is the
     list itself).  ``loss`` / ``loss_scale``: the robust loss (BundleAdjuster;
@@ -83,7 +83,8 @@ def bundle_projective_obs(Pp, Xp, obs_pt, obs_cam, obs_x, *varargin, num_vis=0.0
     ``jacobian="fd" | "analytic"`` (BundleAdjuster) goes with the solver
     keywords.  ``return_covariance`` appends BundleAdjuster.covariance()
     at the returned parameters (the projective model fixes no gauge: expect
-    VlgbaError -1007 or very large values unless the structure is fixed)."""
+    VlgbaError -1007 or very large values unless the structure is fixed), by
+    ``covariance_method`` ("dense", "selected" or None: the default, "dense")."""
     Pp, Xp = _F(Pp), _F(Xp)
     m, n = Pp.shape[2], Xp.shape[1]
     o = parse_options(m, n, varargin, x=np.zeros((2, n, m)))
@@ -99,16 +100,17 @@ def bundle_projective_obs(Pp, Xp, obs_pt, obs_cam, obs_x, *varargin, num_vis=0.0
         a, b = ba.get_params()
         if return_covariance:
             ba.set_params(a, b)   # a linearisation of its own at the returned point
-            cov = ba.covariance(scale=loss == "none")
+            cov = ba.covariance(scale=loss == "none", method=covariance_method)
     out = unpack(a, b, Xp[3:4]) + (err,)
     out = out + (st,) if return_stats else out
     return out + (cov,) if return_covariance else out
 
 
 def bundle_projective(Pp, Xp, x, *varargin, device=0, return_stats=False, semantics="mex",
-                      return_covariance=False, loss="none", loss_scale=0.0, **solver_kw):
+                      return_covariance=False, loss="none", loss_scale=0.0,
+                      covariance_method=None, **solver_kw):
     """[Pp_ Xp_ error_] = bundle_projective(Pp, Xp, x, ...) (bundle_projective.m:1);
-    ``loss`` / ``loss_scale`` as bundle_projective_obs."""
+    ``loss`` / ``loss_scale`` / ``covariance_method`` as bundle_projective_obs."""
     x, Pp = _F(x), _F(Pp)
     m, n = Pp.shape[2], x.shape[1]
     o = parse_options(m, n, varargin, x=x)
@@ -127,7 +129,8 @@ def bundle_projective(Pp, Xp, x, *varargin, device=0, return_stats=False, semant
     return bundle_projective_obs(Pp, Xp, pt, cam, obs_x, *rest, num_vis=num_vis, device=device,
                                  return_stats=return_stats, semantics=semantics,
                                  return_covariance=return_covariance, loss=loss,
-                                 loss_scale=loss_scale, **solver_kw)
+                                 loss_scale=loss_scale, covariance_method=covariance_method,
+                                 **solver_kw)
 
 
 def bundle_projective_nomex(Pp, Xp, x, *varargin, device=0, return_stats=False, loss="none",

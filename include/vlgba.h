@@ -39,7 +39,10 @@ extern "C" {
  * vlgba_covariance, VLGBA_E_SINGULAR; 6 also covers the robust-loss entry
  * points added since (vlgba_set_loss, vlgba_get_loss, vlgba_get_residuals,
  * VLGBA_LOSS_*: entry points only, no struct changed) and the Jacobian-mode
- * ones (vlgba_set_jacobian, vlgba_get_jacobian, VLGBA_JAC_*: likewise).  Callers
+ * ones (vlgba_set_jacobian, vlgba_get_jacobian, VLGBA_JAC_*: likewise) and the
+ * covariance-method ones (vlgba_set_covariance_method,
+ * vlgba_get_covariance_method, vlgba_get_covariance_blocks,
+ * vlgba_debug_selinv_plan, VLGBA_COV_*: likewise).  Callers
  * check it once at load time with VLGBA_ABI_CHECK() (the MEX gateways and the Python
  * loader do): the library compares the version and the struct sizes the
  * caller was compiled with against its own and returns 0 or VLGBA_E_ABI. */
@@ -272,8 +275,9 @@ int vlgba_get_reduced_system(vlgba_ctx *ctx, int *blk_jk, double *blocks, double
  * One rank only: VLGBA_E_ARG for world_size > 1 (with or without a
  * communicator); VLGBA_E_ARG too when rocSOLVER or its dpotrf / dpotri are not
  * available.  Uses 8 ld^2 bytes of device scratch (the pinv fallback's
- * buffer; cfg3: 288 MB).  A selected inverse on the solver's own factors,
- * which avoids the dense ld^2 step, is not built.
+ * buffer; cfg3: 288 MB).  The selected method (vlgba_set_covariance_method
+ * below) avoids the dense ld^2 step on contexts whose reduced solve is the
+ * camera-aligned cyclic reduction.
  * The call leaves the LM state as it was: the next vlgba_step gives the same
  * bits as without it, vlgba_get_step still returns the last pass's step.
  * With a loss set (vlgba_set_loss) the unscaled outputs come from the weighted
@@ -281,6 +285,50 @@ int vlgba_get_reduced_system(vlgba_ctx *ctx, int *blk_jk, double *blocks, double
  * returns VLGBA_E_ARG: sigma2 from a robust cost is not the noise variance. */
 int vlgba_covariance(vlgba_ctx *ctx, int scale, double *cov_a, double *cov_a_full,
                      double *cov_b, double *info);
+/* ---- how vlgba_covariance forms Sigma_a --------------------------------------
+ *   VLGBA_COV_DENSE     the dense inverse described above (default)
+ *   VLGBA_COV_SELECTED  a selected inverse on the factors of the camera-aligned
+ *                       cyclic reduction: Sigma_a only on the tile-tridiagonal
+ *                       pattern of S0, which holds every co-visible block
+ * The selected method assembles S0 in the reduced solve's own tiles, runs the
+ * cyclic reduction's per-level factor launches (no back substitution: the last
+ * pass's step stays), then walks the elimination tree back down, one launch
+ * per level:  for a tile e eliminated between the kept tiles p < e < q, with
+ * L_e = chol(D_e), Mp = L_e^-T L(p, e)^T, Mq = L_e^-T L(q, e)^T,
+ *   Sigma_ep = -(Mp Sigma_pp + Mq Sigma_qp)
+ *   Sigma_eq = -(Mp Sigma_qp^T + Mq Sigma_qq)
+ *   Sigma_ee = L_e^-T L_e^-1 - Sigma_ep Mp^T - Sigma_eq Mq^T
+ * cov_a and the co-visible blocks behind cov_b come out of those tiles; the
+ * point stage is the dense method's kernel on the packed blocks (whatever
+ * VLGBA_COV_PACKED says: that switch concerns the dense method).  Its device
+ * scratch is three 32 x 32 tiles per cyclic-reduction tile (info[6]; cfg3:
+ * 4.9 MB); neither rocSOLVER nor the 8 ld^2 buffer is touched.  info[4] is
+ * then the time of Schur + assembly + factor + descent + extraction.  Fixed
+ * rows, info[0..3], scaling, the loss and Jacobian semantics, the single-rank
+ * rule and "the call leaves the LM state as it was" are the dense method's.  A
+ * non-positive pivot of the cyclic reduction returns VLGBA_E_SINGULAR and
+ * writes no covariance.  Summation order is fixed: a call repeated on the
+ * same state gives the same bits; they differ from the dense method's by
+ * rounding.
+ * vlgba_set_covariance_method: VLGBA_E_ARG for an unknown kind, and for
+ * VLGBA_COV_SELECTED unless the context's reduced solve is the camera-aligned
+ * cyclic reduction (vlgba_plan_info [12] > 0 and [19] == num_a * floor(32 /
+ * num_a)) on one rank, not in ordered or parity mode.  With
+ * VLGBA_COV_SELECTED, vlgba_covariance returns VLGBA_E_ARG when cov_a_full !=
+ * NULL: the full matrix is the dense method's.
+ * Not built: selected inverses on the envelope, nested-dissection and 64-row
+ * cyclic-reduction factors, several ranks, the MATLAB drop-ins. */
+#define VLGBA_COV_DENSE 0
+#define VLGBA_COV_SELECTED 1
+int vlgba_set_covariance_method(vlgba_ctx *ctx, int kind);
+int vlgba_get_covariance_method(vlgba_ctx *ctx, int *kind);
+/* the co-visible blocks Sigma_a[j,k], j >= k, of the last successful
+ * vlgba_covariance call (either method; scaled by sigma2 if that call was), in
+ * the order and layout of vlgba_get_reduced_system: blk_jk [2 * count], blocks
+ * [num_a x num_a x count] column major, count = vlgba_plan_info [10]; both
+ * triangles of a diagonal block are filled.  Either pointer may be NULL.
+ * VLGBA_E_ARG before any successful call. */
+int vlgba_get_covariance_blocks(vlgba_ctx *ctx, int *blk_jk, double *blocks);
 /* ---- robust loss (iteratively reweighted least squares, first order) -----
  * s = e0^2 + e1^2 of an observation in pixels^2, scale c in pixels, w = rho'(s):
  *   VLGBA_LOSS_NONE    rho = s                                     w = 1
@@ -503,6 +551,15 @@ int vlgba_debug_force_status(vlgba_ctx *ctx, int word, int passes);
  * with an earlier arc) and the predicted chain of factor steps (crit).
  * bnd must hold 9 ints. */
 int vlgba_debug_nd_plan(int m, int num_a, const int *blk_jk, int nb, int *bnd, int *crit);
+/* The plan of the selected inverse (VLGBA_COV_SELECTED) on the host (no GPU),
+ * for a cyclic reduction of ntiles >= 1 tiles: the elimination records elim
+ * [3 * ntiles] = (e, p, q), p < e < q the kept neighbours or -1, level by level
+ * (level l: records eptr[l] .. eptr[l+1]-1; eptr must hold 34 ints), and per
+ * record src [2 * ntiles]: the record that holds Sigma_qp and 1 when it is p's
+ * (Sigma_qp = Sigma_pq^T of its q side) or 0 when it is q's (its p side as
+ * stored); -1, 0 where p or q is absent.  Returns the level count, -1 on bad
+ * arguments. */
+int vlgba_debug_selinv_plan(int ntiles, int *elim, int *eptr, int *src);
 
 /* Library / device info: writes a NUL-terminated string, returns its length. */
 int vlgba_version(char *buf, int len);
