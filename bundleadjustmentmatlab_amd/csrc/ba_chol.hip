@@ -2683,9 +2683,6 @@ __global__ __launch_bounds__(256) void k_cr32_back_all(const int *__restrict__ e
 // spin is bounded (timeout word status[1]: the host re-solves with the per-level
 // launches).
 // ---------------------------------------------------------------------------
-#ifndef BA_CR_PW
-#define BA_CR_PW 1
-#endif
 // (the block ranges: cr32_fplan, ba_chol_plan.h)
 
 __device__ __forceinline__ void cr32_wait_flags(const unsigned *flag, int nw, const int w[8],
@@ -2811,11 +2808,11 @@ __global__ __launch_bounds__(256) void k_cr32_fused(double *S, long long lds, in
         }
         // (Tried in round 5: own D_k waited for alone and its loads issued
         // before the neighbours' wait -- 81 -> 86 us: the second poll-and-
-        // barrier costs more than the overlapped loads save.)  BA_CR_PW: the
-        // flags are polled per operand by the wave that loads it
-        // (cr32_level_body), no poll-and-barrier here
+        // barrier costs more than the overlapped loads save.)  The flags are
+        // polled per operand by the wave that loads it (cr32_level_body's pw),
+        // no poll-and-barrier here -- but for a record without a body
         const bool skip = (role == 1 && p < 0) || (role == 2 && q < 0);
-        if (!BA_CR_PW || skip) cr32_wait_flags(flag, nw, w, epoch, status);
+        if (skip) cr32_wait_flags(flag, nw, w, epoch, status);
         CR_ST(1);
         // the survivor's r_k: the neighbours' y and its own r_k of level L-1
         auto mid = [&]() {
@@ -2828,7 +2825,7 @@ __global__ __launch_bounds__(256) void k_cr32_fused(double *S, long long lds, in
         const cr32_pw pw{flag, epoch, status, L, nt};
         if (!skip)
             cr32_level_body<true>(sh, S, lds, TB, ld, k, p, q, em, ep, role, nt, linv, crL, rhs,
-                                  y, status, mid, BA_CR_PW ? &pw : nullptr);
+                                  y, status, mid, &pw);
         CR_ST(2);
         cr32_publish(flag + fw(L, k, role == 3 ? 4 : role), epoch);
         CR_ST(3);
@@ -3556,6 +3553,15 @@ int ba_cr32_selinv_sources(const ba_dev *d, int *src)
     return 0;
 }
 
+// the whole CR in one launch (JAC: the table its folded camera update builds)
+template <bool JAC>
+static void launch_cr32_fused(ba_dev *d, const cr32_fplan &P, const cr32_camupd &cu)
+{
+    k_cr32_fused<JAC><<<P.b0[P.nl] + P.nrec, 256, 0, d->stream>>>(
+        d->S, d->lds, d->tb32, d->ld, d->cr_elim, d->crf, d->crs, d->nt32, d->linv, d->crL,
+        d->rhs, d->ywork, d->da, d->crflag, d->xgran, d->back_epoch, d->scal + 4, P, cu);
+}
+
 int ba_chol_solve(ba_dev *d, int nospin)
 {
     const int nt = d->nt;
@@ -3574,7 +3580,6 @@ int ba_chol_solve(ba_dev *d, int nospin)
     }
     if (d->cr_nlev > 0 && d->cr32 && d->cr_fused && d->crflag && !nospin) {   // one launch
         const cr32_fplan &P = d->plan->fplan;
-        const int nl = P.nl, nrec = P.nrec;
         if (++d->back_epoch == 0) d->back_epoch = 1;
         cr32_camupd cu{};
         if (d->camupd_fold) {   // the next update launches no k_camera_update
@@ -3582,16 +3587,8 @@ int ba_chol_solve(ba_dev *d, int nospin)
             d->camupd_done = 1;
         }
         KT_B(d);
-        if (d->jac)
-            k_cr32_fused<true><<<P.b0[nl] + nrec, 256, 0, d->stream>>>(
-                d->S, d->lds, d->tb32, d->ld, d->cr_elim, d->crf, d->crs, d->nt32, d->linv,
-                d->crL, d->rhs, d->ywork, d->da, d->crflag, d->xgran, d->back_epoch,
-                d->scal + 4, P, cu);
-        else
-            k_cr32_fused<false><<<P.b0[nl] + nrec, 256, 0, d->stream>>>(
-                d->S, d->lds, d->tb32, d->ld, d->cr_elim, d->crf, d->crs, d->nt32, d->linv,
-                d->crL, d->rhs, d->ywork, d->da, d->crflag, d->xgran, d->back_epoch,
-                d->scal + 4, P, cu);
+        if (d->jac) launch_cr32_fused<true>(d, P, cu);
+        else launch_cr32_fused<false>(d, P, cu);
         KT_E(d, KT_CR_FACTOR);
         return -(int)hipGetLastError();
     }

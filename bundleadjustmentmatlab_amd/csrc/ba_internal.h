@@ -69,11 +69,6 @@ struct ba_flags {
     int has_pivot;      // pivot[m] mask      (:150-154)
 };
 
-// the camera reduction's arguments (k_camera_reduce_chunks, or workgroups
-// appended to the MFMA Schur launch)
-#ifndef BA_FUSE_CAMRED
-#define BA_FUSE_CAMRED 1
-#endif
 // robust loss of the fast path (vlgba_set_loss; vlg_loss in ba_kernels.hip):
 // kind 0 none, 1 Huber, 2 Cauchy; c the scale in pixels
 struct ba_loss {
@@ -81,6 +76,8 @@ struct ba_loss {
     double c;
 };
 
+// the camera reduction's arguments (k_camera_reduce_chunks, or workgroups
+// appended to the MFMA Schur launch: every plan with MFMA groups)
 struct ba_camred {
     const int *cam_eptr, *cam_eslots;
     const double *upart;
@@ -224,7 +221,6 @@ struct ba_dev {
                        // LM trajectory with the oracle)
     ba_camred camred;            // this pass's camera reduction
     int camred_pending;          // ... to run inside the MFMA Schur launch
-    int fuse_camred;             // 1: it may (fast path, MFMA groups)
     int mfma;          // fast path: 1 = some MFMA Schur chunks (k_schur_mfma: groups
                        // [0, ngrp_mf)), 0 = term lists only (k_schur_group)
     int no_mfma;       // option: force the term-list Schur kernel
@@ -337,7 +333,7 @@ struct ba_dev {
 #define BA_PART_MAX 65536
 
 // ---- ba_kernels.hip ----
-int ba_launch_rotations(ba_dev *d, const double *a, double *rot, int all5);
+int ba_launch_rotations(ba_dev *d, const double *a, double *rot);
 int ba_launch_linearize(ba_dev *d, ba_flags f);
 // fuse = 1 (an LM pass whose MFMA Schur launch follows): only records the
 // reduction for that launch when the plan has MFMA groups

@@ -327,12 +327,6 @@ __global__ __launch_bounds__(256) void k_linearize(
 // U_j / eA_j (sequential over the chunk's points), reduced per camera in chunk
 // order by k_camera_reduce_chunks.  jrec is never written.
 // -------------------------------------------------------------------------
-// 7 waves per SIMD for NA = 6: the LDS rows (21.7 KB) allow 7 workgroups per
-// CU; the bound keeps the register allocation from costing one of them
-#ifndef BA_LIN_W2_ON
-#define BA_LIN_W2_ON 1
-#endif
-
 // UPD = true (k_update_linearize): the point update of the pass that just
 // solved (mex_bundle_3_db_new.c:99-146: db_i, b_new, the point part of
 // dp'(lambda dp + g)) runs first in the same workgroup, from the pass's W / eB
@@ -352,15 +346,11 @@ __global__ __launch_bounds__(256) void k_linearize(
 // (profiles/r06/ab_lin_cams.txt).  Chunks whose cameras span more than
 // BA_LIN_CAMS read the table from memory as before.  The same values: bit for
 // bit the same columns.  (Staging a and K4 as well measured 326-328 us.)  0: off.
-#ifndef BA_LIN_CAMS
 #define BA_LIN_CAMS 10
-#endif
 // waves per SIMD the NA = 6 linearisation kernels are compiled for: 6 with the
 // staged cameras (80 VGPRs; their LDS allows 6 workgroups per CU), else 7 (72
 // VGPRs, 7 workgroups per CU)
-#ifndef BA_LIN_WAVES
 #define BA_LIN_WAVES (BA_LIN_CAMS > 0 ? 6 : 7)
-#endif
 
 struct ba_upd {
     const double *W_old, *da, *eB_old, *Vinv, *b_old;
@@ -716,8 +706,8 @@ __device__ __forceinline__ void linearize_chunk_body(
     }
     // W_ij = A^T B onto a zeroed output (:305-314): the chunk's W rows are one
     // contiguous HBM range, written lane by lane (coalesced), two entries
-    // (rows r, r + 1 of one column) per lane
-    if constexpr (BA_LIN_W2_ON && NA % 2 == 0) {
+    // (rows r, r + 1 of one column) per lane where NA is even
+    if constexpr (NA % 2 == 0) {
         double2 *wdst = reinterpret_cast<double2 *>(W + (size_t)3 * NA * obase);
         constexpr int NP = 3 * NA / 2;         // entry pairs per observation
         for (int q = tid; q < nobs * NP; q += 256) {
@@ -1330,37 +1320,62 @@ __global__ __launch_bounds__(256) void k_schur_group(
 // -------------------------------------------------------------------------
 // V*^-1 per point (bundle_euclid.m:168-180) for the MFMA Schur path
 // -------------------------------------------------------------------------
-// (the block's 256 contiguous 9-double rows in and out through LDS, lane by
-// lane: every cache line requested once)
+// The damped vlg_pinv3 of the points [p0, p1) by one 256-thread workgroup,
+// 256 points a step: the batch's contiguous 9-double rows go in and out
+// through the caller's LDS stage (>= 256 x 9 doubles), lane by lane, so every
+// cache line is requested once, and the next batch's rows are in flight under
+// this batch's inverses.  The stage is free again on return.  Its pointer is
+// typed as LDS: the routine's addressing is then optimised for LDS before it
+// is inlined, which leaves k_schur_mfma with exactly the instructions of the
+// loop that once stood there (a generic pointer changes its address
+// arithmetic).
+typedef __attribute__((address_space(3))) double lds_double;
+__device__ __forceinline__ void point_vinv_range(const double *V, double *Vinv, int p0, int p1,
+                                                 double lambda, lds_double *stage)
+{
+    const int tid = threadIdx.x;
+    double t[9];
+    auto rows = [&](int i0) {   // the batch's rows, lane by lane
+        const int cnt = 9 * min(256, p1 - i0);
+        const double *src = V + 9 * (size_t)i0;
+#pragma unroll
+        for (int u = 0; u < 9; u++) t[u] = tid + 256 * u < cnt ? src[tid + 256 * u] : 0.0;
+    };
+    if (p0 < p1) rows(p0);
+    for (int i0 = p0; i0 < p1; i0 += 256) {
+        const int cnt = 9 * min(256, p1 - i0);
+#pragma unroll
+        for (int u = 0; u < 9; u++) stage[tid + 256 * u] = t[u];
+        __syncthreads();
+        if (i0 + 256 < p1) rows(i0 + 256);   // in flight under this batch's inverses
+        if (i0 + tid < p1) {
+            double vs[9], vi[9];
+#pragma unroll
+            for (int q = 0; q < 9; q++) vs[q] = stage[9 * tid + q];
+#pragma unroll
+            for (int c = 0; c < 3; c++) vs[4 * c] = (1 + lambda) * vs[4 * c];
+            vlg_pinv3(vs, vi);
+#pragma unroll
+            for (int q = 0; q < 9; q++) stage[9 * tid + q] = vi[q];
+        }
+        __syncthreads();
+        double *dst = Vinv + 9 * (size_t)i0;
+#pragma unroll
+        for (int u = 0; u < 9; u++)
+            if (tid + 256 * u < cnt) dst[tid + 256 * u] = stage[tid + 256 * u];
+        __syncthreads();
+    }
+}
+
+// one 256-point batch per workgroup (the pass's own launch when the MFMA Schur
+// kernel does not fold V*^-1 into its prologue)
 template <int NA>
 __global__ __launch_bounds__(256) void k_point_vinv(const double *__restrict__ V, int n,
                                                     double lambda, double *__restrict__ Vinv)
 {
     __shared__ double vsh[256 * 9];
-    const int i0 = blockIdx.x * 256, tid = threadIdx.x;
-    const int cnt = 9 * min(256, n - i0);
-    const double *src = V + 9 * (size_t)i0;
-    double t[9];
-#pragma unroll
-    for (int u = 0; u < 9; u++) t[u] = tid + 256 * u < cnt ? src[tid + 256 * u] : 0.0;
-#pragma unroll
-    for (int u = 0; u < 9; u++) vsh[tid + 256 * u] = t[u];
-    __syncthreads();
-    if (i0 + tid < n) {
-        double vs[9], vi[9];
-#pragma unroll
-        for (int q = 0; q < 9; q++) vs[q] = vsh[9 * tid + q];
-#pragma unroll
-        for (int c = 0; c < 3; c++) vs[4 * c] = (1 + lambda) * vs[4 * c];
-        vlg_pinv3(vs, vi);
-#pragma unroll
-        for (int q = 0; q < 9; q++) vsh[9 * tid + q] = vi[q];
-    }
-    __syncthreads();
-    double *dst = Vinv + 9 * (size_t)i0;
-#pragma unroll
-    for (int u = 0; u < 9; u++)
-        if (tid + 256 * u < cnt) dst[tid + 256 * u] = vsh[tid + 256 * u];
+    const int i0 = blockIdx.x * 256;
+    point_vinv_range(V, Vinv, i0, min(i0 + 256, n), lambda, (lds_double *)vsh);
 }
 
 // -------------------------------------------------------------------------
@@ -1394,9 +1409,6 @@ __global__ __launch_bounds__(256) void k_point_vinv(const double *__restrict__ V
 // deterministic run to run; only the grouping differs from the term kernel.
 // -------------------------------------------------------------------------
 #define BA_MF_KB 5   // points per K-block (one wave)
-#ifndef BA_MF_ROW4
-#define BA_MF_ROW4 1
-#endif
 // lane (lk, 4 b + i) <- lane (lk, 4 rg + i) within each 16-lane row (ds_swizzle
 // bit mask mode on 32-lane halves: and 0x13 keeps bit 4 and the row i, or sets
 // the row group)
@@ -1417,28 +1429,22 @@ __device__ __forceinline__ double row4_bcast(double v, int rg)
     default: return row4_bcast_c<3>(v);
     }
 }
-#ifndef BA_MF_PIPE
-#define BA_MF_PIPE 0
-#endif
-// BA_MF_GATHER: the 16 lanes of a row need the same V*^-1 and eB entries (the
-// row's point), so each row loads them once -- lane li one entry -- and the
-// chunk's processing broadcasts them (DPP row_newbcast): one load per lane
-// instead of ten, a fifth of the kernel's vector-memory data traffic (TD
-// busy 78 %, profiles/r06/pmc_cfg3_summary.csv), and 18 fewer VGPRs held
-// per chunk in flight.  The same values: bit-identical.
-#ifndef BA_MF_GATHER
-#define BA_MF_GATHER 1
-#endif
-// lane Q's value to every lane of its 16-lane row (v_mov_b64 DPP row_newbcast)
+// lane Q's value to every lane of its 16-lane row (v_mov_b64 DPP row_newbcast).
+// The 16 lanes of a row need the same V*^-1 and eB entries (the row's point),
+// so each row loads them once -- lane li one entry -- and the chunk's
+// processing broadcasts them with this: one load per lane instead of ten, a
+// fifth of the kernel's vector-memory data traffic (TD busy 78 %,
+// profiles/r06/pmc_cfg3_summary.csv), and 18 fewer VGPRs held per chunk in
+// flight than with every lane loading its own ten.  The same values:
+// bit-identical.
 template <int Q> __device__ __forceinline__ double row16_bcast_c(double v)
 {
     const long long u = __builtin_bit_cast(long long, v);
     const long long r = __builtin_amdgcn_mov_dpp(u, 0x150 + Q, 0xf, 0xf, true);   // v_mov_b64_dpp
     return __builtin_bit_cast(double, r);
 }
-#ifndef BA_MF_WAVES
+// waves per SIMD the NA = 6 kernel is compiled for
 #define BA_MF_WAVES 3
-#endif
 template <int NA>
 __global__ __launch_bounds__(256, (NA == 6) ? BA_MF_WAVES : 1) void k_schur_mfma(
     const int *__restrict__ grp_ch, const int *__restrict__ grp_gs,
@@ -1476,45 +1482,12 @@ __global__ __launch_bounds__(256, (NA == 6) ? BA_MF_WAVES : 1) void k_schur_mfma
     const int rb0 = ch_blob[c0], nrw = ch_blob[c0 + nc] - rb0;
     if (Vdamp) {
         // V*^-1 of the group's own points (ba_dev::vinv_fold: the MFMA groups'
-        // ranges tile every point, so no k_point_vinv launch): k_point_vinv's
-        // damped vlg_pinv3 on the same inputs, 256 points a step, their 9-double
-        // rows in and out through the LDS pool (>= 256 x 9 doubles then) before
-        // the accumulators and records below take it: every cache line
-        // requested once.  Vinv is not __restrict__: the barrier ahead of the
-        // chunk loop orders these stores before its loads of them (the same
-        // workgroup, the same CU).
-        const int p0 = ch_pt[c0], p1 = ch_pt[c0 + nc];
-        double t[9];
-        auto rows = [&](int i0) {   // the batch's rows, lane by lane
-            const int cnt = 9 * min(256, p1 - i0);
-            const double *src = Vdamp + 9 * (size_t)i0;
-#pragma unroll
-            for (int u = 0; u < 9; u++) t[u] = tid + 256 * u < cnt ? src[tid + 256 * u] : 0.0;
-        };
-        if (p0 < p1) rows(p0);
-        for (int i0 = p0; i0 < p1; i0 += 256) {
-            const int cnt = 9 * min(256, p1 - i0);
-#pragma unroll
-            for (int u = 0; u < 9; u++) sm[tid + 256 * u] = t[u];
-            __syncthreads();
-            if (i0 + 256 < p1) rows(i0 + 256);   // in flight under this batch's inverses
-            if (i0 + tid < p1) {
-                double vs[9], vi[9];
-#pragma unroll
-                for (int q = 0; q < 9; q++) vs[q] = sm[9 * tid + q];
-#pragma unroll
-                for (int c = 0; c < 3; c++) vs[4 * c] = (1 + lambda) * vs[4 * c];
-                vlg_pinv3(vs, vi);
-#pragma unroll
-                for (int q = 0; q < 9; q++) sm[9 * tid + q] = vi[q];
-            }
-            __syncthreads();
-            double *dst = Vinv + 9 * (size_t)i0;
-#pragma unroll
-            for (int u = 0; u < 9; u++)
-                if (tid + 256 * u < cnt) dst[tid + 256 * u] = sm[tid + 256 * u];
-            __syncthreads();
-        }
+        // ranges tile every point, so no k_point_vinv launch): the same routine
+        // on the same inputs, staged in the LDS pool (>= 256 x 9 doubles then)
+        // before the accumulators and records below take it.  Vinv is not
+        // __restrict__: the barrier ahead of the chunk loop orders these stores
+        // before its loads of them (the same workgroup, the same CU).
+        point_vinv_range(Vdamp, Vinv, ch_pt[c0], ch_pt[c0 + nc], lambda, (lds_double *)sm);
     }
     for (int q = tid; q < ngs * NA * NA; q += 256) gacc[q] = 0.0;
     for (int q = tid; q < nge * NA; q += 256) geacc[q] = 0.0;
@@ -1536,13 +1509,12 @@ __global__ __launch_bounds__(256, (NA == 6) ? BA_MF_WAVES : 1) void k_schur_mfma
     // Absent entries read the exact zeros of the row past the end of W / V*^-1 /
     // eB (no select after a load: its wait lands at the MFMA that consumes it);
     // addresses are a uniform chunk base plus a 32-bit lane offset.
-    // vf: V*^-1 of point 5w + lk, entries (0,0) (1,0) (2,0) (1,1) (2,1) (2,2)
-    // (symmetric); vf[6]: the s = 3 Y MFMA's A fragment V*^-1[lk][li] of point
-    // 5w + 4 (zero outside rows li < 3, K lk < 3)
-    auto load = [&](int k, double (&wf)[4][RT], double (&vf)[7], double (&ef)[4]) {
-        // BA_MF_GATHER: vf[0] holds the row's gathered entry (lane li: V*^-1
-        // entry li < 6, eB entry li - 6 < 3, eB of point 5 w + 4 for li >= 9),
-        // vf[6] as before; the rest is formed by process()
+    // vg: the row's gathered entry of point 5w + lk -- lane li < 6: V*^-1 entry
+    // (0,0) (1,0) (2,0) (1,1) (2,1) (2,2) (symmetric), li - 6 < 3: eB entry,
+    // li >= 9: eB[lk] of point 5w + 4 -- which process() broadcasts along the
+    // row; v4: the s = 3 Y MFMA's A fragment V*^-1[lk][li] of point 5w + 4
+    // (zero outside rows li < 3, K lk < 3)
+    auto load = [&](int k, double (&wf)[4][RT], double &vg, double &v4) {
         const unsigned *r = rec + gbo[k];
         const int np = gp0[k + 1] - gp0[k], i0 = gp0[k], ob = gob[k];
         const int C = (int)(r[1] & 0xffu);
@@ -1566,29 +1538,14 @@ __global__ __launch_bounds__(256, (NA == 6) ? BA_MF_WAVES : 1) void k_schur_mfma
             for (int s = 0; s < 3; s++) wf[s][t] = wbase[oA + NA * s];
             wf[3][t] = wbase[o4];
         }
-        if (BA_MF_GATHER) {
-            // V*^-1 entries (0,0) (1,0) (2,0) (1,1) (2,1) (2,2) -> lanes 0..5
-            const int vo = li + (li >= 3 ? 1 : 0) + (li >= 5 ? 2 : 0);
-            const double *src = li < 6   ? vbase + (pvA ? 9 * pA + vo : vz)
-                                : li < 9 ? ebase + (pvA ? 3 * pA + li - 6 : ez)
-                                         : ebase + (pv4 ? 3 * p4 + lk : ez);
-            vf[0] = *src;
-            const bool dv = p4 < np && li < 3 && lk < 3;
-            vf[6] = vbase[dv ? 9 * p4 + lk + 3 * li : vz];
-        } else {
-            const int oe = pvA ? 3 * pA : ez;
-#pragma unroll
-            for (int s = 0; s < 3; s++) ef[s] = ebase[oe + s];
-            ef[3] = ebase[pv4 ? 3 * p4 + lk : ez];
-            const int ov = pvA ? 9 * pA : vz;
-#pragma unroll
-            for (int u = 0; u < 6; u++) {
-                constexpr int off[6] = {0, 1, 2, 4, 5, 8};
-                vf[u] = vbase[ov + off[u]];
-            }
-            const bool dv = p4 < np && li < 3 && lk < 3;
-            vf[6] = vbase[dv ? 9 * p4 + lk + 3 * li : vz];
-        }
+        // V*^-1 entries (0,0) (1,0) (2,0) (1,1) (2,1) (2,2) -> lanes 0..5
+        const int vo = li + (li >= 3 ? 1 : 0) + (li >= 5 ? 2 : 0);
+        const double *src = li < 6   ? vbase + (pvA ? 9 * pA + vo : vz)
+                            : li < 9 ? ebase + (pvA ? 3 * pA + li - 6 : ez)
+                                     : ebase + (pv4 ? 3 * p4 + lk : ez);
+        vg = *src;
+        const bool dv = p4 < np && li < 3 && lk < 3;
+        v4 = vbase[dv ? 9 * p4 + lk + 3 * li : vz];
     };
     d4 accS[NTL];
     double eacc[RT];
@@ -1597,51 +1554,30 @@ __global__ __launch_bounds__(256, (NA == 6) ? BA_MF_WAVES : 1) void k_schur_mfma
 #pragma unroll
     for (int t = 0; t < RT; t++) eacc[t] = 0.0;
     // one chunk: Y tiles, e_ sums, lower S tiles; flush at a change of cameras
-    auto process = [&](int k, const double (&wc)[4][RT], const double (&vg)[7],
-                       const double (&eg)[4]) {
-        double vc[7], ec[4];
-        if (BA_MF_GATHER) {   // the row's entries from its lanes 0..9
-            vc[0] = row16_bcast_c<0>(vg[0]);
-            vc[1] = row16_bcast_c<1>(vg[0]);
-            vc[2] = row16_bcast_c<2>(vg[0]);
-            vc[3] = row16_bcast_c<3>(vg[0]);
-            vc[4] = row16_bcast_c<4>(vg[0]);
-            vc[5] = row16_bcast_c<5>(vg[0]);
-            vc[6] = vg[6];
-            ec[0] = row16_bcast_c<6>(vg[0]);
-            ec[1] = row16_bcast_c<7>(vg[0]);
-            ec[2] = row16_bcast_c<8>(vg[0]);
-            ec[3] = row16_bcast_c<9>(vg[0]);
-        } else {
-#pragma unroll
-            for (int u = 0; u < 7; u++) vc[u] = vg[u];
-#pragma unroll
-            for (int s = 0; s < 4; s++) ec[s] = eg[s];
-        }
+    auto process = [&](int k, const double (&wc)[4][RT], double vg, double v4) {
+        // the row's entries from its lanes 0..9: V*^-1 of the lane's own point
+        // (the six entries in load()'s order) and the eB of its four K steps
+        const double vc[6] = {row16_bcast_c<0>(vg), row16_bcast_c<1>(vg), row16_bcast_c<2>(vg),
+                              row16_bcast_c<3>(vg), row16_bcast_c<4>(vg), row16_bcast_c<5>(vg)};
+        const double ec[4] = {row16_bcast_c<6>(vg), row16_bcast_c<7>(vg), row16_bcast_c<8>(vg),
+                              row16_bcast_c<9>(vg)};
         const unsigned *r = rec + gbo[k];
         const unsigned h1 = r[1];
         const int C = (int)(h1 & 0xffu), fl = (int)((h1 >> 8) & 0xffu), Rc = NA * C;
         // row tile by row tile: one Y tile live at a time.  Every tile runs (tiles
         // past the chunk's columns multiply exact zeros): no branch between the
         // next chunk's loads and the MFMAs, so their waits stay precise
-        // s = 3 first, all column tiles: point 5w + 4 on the matrix pipe
-        // (register 0 = A fragment), in flight while the VALU forms the rest
+        // s = 3 first, all column tiles: point 5w + 4 on the matrix pipe, in
+        // flight while the VALU forms the rest.  v_mfma_f64_4x4x4: block
+        // b = li >> 2 takes V*^-1 rows (li & 3) (the A fragment's first block,
+        // swizzled to all four) against columns 16 ti + li and leaves row lk,
+        // column 16 ti + li: register 0 of the 16x16x4 form (which this once
+        // was), at a sixth of its matrix-pipe time
         double y4[RT];
-        if (BA_MF_ROW4) {
-            // v_mfma_f64_4x4x4: block b = li >> 2 takes V*^-1 rows (li & 3) (the
-            // A fragment's first block, swizzled to all four) against columns
-            // 16 ti + li and leaves row lk, column 16 ti + li: register 0 of
-            // the 16x16x4 form, at a sixth of its matrix-pipe time
-            const double va = row4_bcast(vc[6], 0);
+        const double va = row4_bcast(v4, 0);
 #pragma unroll
-            for (int ti = 0; ti < RT; ti++)
-                y4[ti] = __builtin_amdgcn_mfma_f64_4x4x4f64(va, wc[3][ti], 0.0, 0, 0, 0);
-        } else {
-#pragma unroll
-            for (int ti = 0; ti < RT; ti++)
-                y4[ti] = __builtin_amdgcn_mfma_f64_16x16x4f64(vc[6], wc[3][ti],
-                                                              d4{0.0, 0.0, 0.0, 0.0}, 0, 0, 0)[0];
-        }
+        for (int ti = 0; ti < RT; ti++)
+            y4[ti] = __builtin_amdgcn_mfma_f64_4x4x4f64(va, wc[3][ti], 0.0, 0, 0, 0);
 #pragma unroll
         for (int ti = 0; ti < RT; ti++) {
             {
@@ -1653,7 +1589,7 @@ __global__ __launch_bounds__(256, (NA == 6) ? BA_MF_WAVES : 1) void k_schur_mfma
                 y[2] = fma(wc[2][ti], vc[5], fma(wc[1][ti], vc[4], wc[0][ti] * vc[2]));
                 eacc[ti] = fma(y[3], ec[3], fma(y[2], ec[2], fma(y[1], ec[1],
                                                                  fma(y[0], ec[0], eacc[ti]))));
-                if (BA_MF_ROW4 && NA == 6 && ti == RT - 1) {
+                if (NA == 6 && ti == RT - 1) {
                     // the last row tile holds NA C - 32 real rows (4 for the usual
                     // six-camera chunk): v_mfma_f64_4x4x4 per group of 4 rows
                     // (tools/ubench_mfma4x4.hip: a sixth of the 16x16x4 time).
@@ -1735,25 +1671,14 @@ __global__ __launch_bounds__(256, (NA == 6) ? BA_MF_WAVES : 1) void k_schur_mfma
             for (int u = 0; u < NTL; u++) accS[u] = d4{0.0, 0.0, 0.0, 0.0};
         }
     };
-    // two register sets, software pipelined: the next chunk's fragments are in
-    // flight while this chunk's MFMAs run (no register copies between sets)
-#if BA_MF_PIPE
-    double wa[4][RT], da[7], ea[4], wb[4][RT], db[7], eb[4];
-    load(0, wa, da, ea);
-    for (int k = 0; k < nc; k += 2) {
-        load(min(k + 1, nc - 1), wb, db, eb);   // unconditional: a clamped reload at the end
-        process(k, wa, da, ea);
-        if (k + 1 >= nc) break;
-        load(min(k + 2, nc - 1), wa, da, ea);
-        process(k + 1, wb, db, eb);
-    }
-#else
-    double wa[4][RT], da[7], ea[4];
+    // one register set, chunk after chunk: the SIMD's other waves cover a
+    // chunk's loads (a second, software-pipelined register set was tried and
+    // never became the default)
+    double wa[4][RT], vg, v4;
     for (int k = 0; k < nc; k++) {
-        load(k, wa, da, ea);
-        process(k, wa, da, ea);
+        load(k, wa, vg, v4);
+        process(k, wa, vg, v4);
     }
-#endif
     __syncthreads();
     for (int q = tid; q < ngs * NA * NA; q += 256) spart[(size_t)NA * NA * gs0 + q] = gacc[q];
     for (int q = tid; q < nge * NA; q += 256) epart[(size_t)NA * ge0 + q] = geacc[q];
@@ -2688,9 +2613,8 @@ static inline int grid_for(long long work, int bs, int cap)
 
 static const int PT_GRID_CAP = 8192;  // partial-sum slots used by per-point kernels
 
-int ba_launch_rotations(ba_dev *d, const double *a, double *rot, int all5)
+int ba_launch_rotations(ba_dev *d, const double *a, double *rot)
 {
-    (void)all5;
     if (d->na == BA_PROJ_NA) return 0;   // projective camera: no rotations
     const int g = grid_for(d->m, 64, 1 << 30);
     KT_B(d);
@@ -2762,7 +2686,7 @@ int ba_launch_camera_reduce(ba_dev *d, ba_flags f, int fuse)
         // after U | eA (all-reduced together with them)
         d->camred = ba_camred{d->cam_eptr, d->cam_eslots, d->upart, d->m, f, d->pivot,
                               d->U, d->eA, d->chsse, d->nch, d->scal + 0, d->eA + d->ld};
-        if (fuse && d->ngrp_mf > 0 && d->fuse_camred) {   // run by this pass's MFMA Schur launch
+        if (fuse && d->ngrp_mf > 0) {   // run by this pass's MFMA Schur launch
             d->camred_pending = 1;
             return 0;
         }
@@ -2800,14 +2724,11 @@ int ba_launch_schur(ba_dev *d, double lambda)
     return -(int)hipGetLastError();
 }
 
-#ifndef BA_SCHUR_TWO_STREAMS
-#define BA_SCHUR_TWO_STREAMS 1
-#endif
 template <int NA>
 static int launch_schur_fast(ba_dev *d, double lambda)
 {
     // MFMA groups [0, ngrp_mf), then the per-term groups [ngrp_mf, ngrp)
-    const bool two = BA_SCHUR_TWO_STREAMS && d->ngrp_mf > 0 && d->ngrp > d->ngrp_mf &&
+    const bool two = d->ngrp_mf > 0 && d->ngrp > d->ngrp_mf &&
                      !d->join_pending && d->side && !(d->kt && d->kt->on);
     if (d->ngrp_mf > 0) {
         // vinv_fold: every point's V*^-1 is formed by its own MFMA group
@@ -2952,27 +2873,14 @@ int ba_launch_assemble(ba_dev *d)
     return 0;
 }
 
-// The fused update (d->fused, fast path): k_camera_update, the long tracks'
-// db, then ONE pass over the observations -- the point update and the
-// linearisation at (a_new, b_new) into the second buffers (k_linearize_chunk
-// with UPD: W2, V2, eB2, upart2, chsse2) -- and the pass's final sums: the new
-// SSE is the sum of the new linearisation's per-chunk SSE partials.  lm_apply
-// swaps the buffers when the step is accepted; a rejected step keeps the
-// pass's own linearisation (App. A Q12).
-// k_sum_parts3's third block forms the camera partials itself (ba_sum3::cam_da)
-static void sum3_camera_dpg(ba_dev *d, double lam_dpg, ba_sum3 *s3)
+// ---- the update (ba_launch_update) and the steps its branches share ----
+// The camera update: k_camera_update, or its analytic-Jacobian twin
+// (ba_dev::jac) -- unless folded: a_new and rot_new are then the solve's
+// (ba_dev::camupd_done)
+static int launch_camera_update(ba_dev *d, int gc, double lam_dpg, bool folded)
 {
-    s3->cam_da = d->da;
-    s3->cam_eA = d->eA;
-    s3->cam_part = d->part;
-    s3->cam_m = d->m;
-    s3->cam_na = d->na;
-    s3->cam_lambda = lam_dpg;
-}
-
-// k_camera_update, or its analytic-Jacobian twin (ba_dev::jac)
-static int launch_camera_update(ba_dev *d, int gc, double lam_dpg)
-{
+    if (folded) return 0;
+    KT_B(d);
     if (d->jac) {
         BA_DISPATCH(d->na, (k_camera_update_jac<NA><<<gc, 320, 0, d->stream>>>(
                                d->a, d->da, d->eA, d->m, lam_dpg, d->a_new, d->rot_new,
@@ -2982,38 +2890,41 @@ static int launch_camera_update(ba_dev *d, int gc, double lam_dpg)
                                d->a, d->da, d->eA, d->m, lam_dpg, d->a_new, d->rot_new,
                                d->part)));
     }
+    KT_E(d, KT_CAMUPD);
     return 0;
 }
 
-static int launch_update_fused(ba_dev *d, double lambda, ba_flags f, bool folded)
+// long tracks: db, b_new, dp'g over all their observations (inside the
+// caller's timing bracket)
+static int launch_long_db(ba_dev *d, double lambda)
 {
-    const int gc = (d->m + 63) / 64;
-    const double lam_dpg = d->dpg_lambda ? lambda : 0.0;
-    if (!folded) {   // (folded: a_new and rot_new are the solve's, ba_dev::camupd_done)
-        KT_B(d);
-        if (const int rc = launch_camera_update(d, gc, lam_dpg)) return rc;
-        KT_E(d, KT_CAMUPD);
-    }
-    KT_B(d);
-    if (d->nl > 0)   // long tracks: db, b_new, dp'g over all their observations
+    if (d->nl > 0)
         BA_DISPATCH(d->na, (k_long_db<NA><<<d->nl, 256, 0, d->stream>>>(
                                d->long_pt, d->long_o0, d->obs_cam, d->W, d->da, d->eB,
                                d->Vinv, d->b, d->ndb, lambda, d->db, d->b_new,
                                d->dpg_long)));
-    const ba_upd u{d->W, d->da, d->eB, d->Vinv, d->b, d->ndb, lambda, d->db, d->b_new,
-                   d->chsse2 + 2 * (size_t)d->nch, d->seg_long, d->long_o0, d->dpg_long};
-    BA_DISPATCH(d->na, (lin_chunk_launch<NA>(d, f, d->a_new, d->rot_new, d->b_new, d->W2,
-                                             d->V2, d->eB2, d->upart2, d->chsse2, &u)));
-    if (d->nl > 0)   // long tracks: V2 / eB2 = sum of their segments' partials
-        k_long_vsum<<<d->nl, 64, 0, d->stream>>>(d->long_pt, d->long_seg0, d->vseg, d->V2,
-                                                 d->eB2);
-    KT_E(d, KT_LIN_UPD);
-    // new SSE (= the new linearisation's SSE), point dpg, camera dpg: one launch
-    ba_sum3 s3 = {{d->chsse2, d->chsse2 + 2 * (size_t)d->nch, d->part},
+    return 0;
+}
+
+// The chunked updates' final sums, one launch: new SSE and point dpg from the
+// per-chunk partials, camera dpg from k_camera_update's partials -- or, when
+// folded, from da and eA by k_sum_parts3's third block itself
+// (ba_sum3::cam_da).  A requested publish rides on it.
+static int launch_final_sums(ba_dev *d, const double *sse_part, const double *dpg_part, int gc,
+                             double lam_dpg, bool folded)
+{
+    ba_sum3 s3 = {{sse_part, dpg_part, d->part},
                   {d->nch, d->nch, gc},
                   {d->scal + 1, d->scal + 3, d->scal + 2},
                   d->scal, nullptr, 0.0, d->pub_cnt};
-    if (folded) sum3_camera_dpg(d, lam_dpg, &s3);
+    if (folded) {
+        s3.cam_da = d->da;
+        s3.cam_eA = d->eA;
+        s3.cam_part = d->part;
+        s3.cam_m = d->m;
+        s3.cam_na = d->na;
+        s3.cam_lambda = lam_dpg;
+    }
     if (d->publish_req) {
         d->seq++;
         s3.hres = d->hres_dev;
@@ -3025,6 +2936,15 @@ static int launch_update_fused(ba_dev *d, double lambda, ba_flags f, bool folded
     return -(int)hipGetLastError();
 }
 
+// The update.  Fused (d->fused, fast path): k_camera_update, the long tracks'
+// db, then ONE pass over the observations -- the point update and the
+// linearisation at (a_new, b_new) into the second buffers (k_linearize_chunk
+// with UPD: W2, V2, eB2, upart2, chsse2) -- and the pass's final sums: the new
+// SSE is the sum of the new linearisation's per-chunk SSE partials.  lm_apply
+// swaps the buffers when the step is accepted; a rejected step keeps the
+// pass's own linearisation (App. A Q12).  Chunked (VLGBA_FUSED=0): the same
+// with k_point_update_chunk for the one pass and no linearisation.  Else the
+// per-point update and its three sums.
 int ba_launch_update(ba_dev *d, double lambda, ba_flags f)
 {
     // the camera update of the one-launch CR that ran directly before
@@ -3033,22 +2953,28 @@ int ba_launch_update(ba_dev *d, double lambda, ba_flags f)
     const bool chunked = !d->ordered && d->nch > 0 && !d->obs_vis && !d->xh_out;
     const bool folded = d->camupd_done && (d->fused || chunked);
     d->camupd_done = 0;
-    if (d->fused) return launch_update_fused(d, lambda, f, folded);
     const int gc = (d->m + 63) / 64;
     // lambda dp'dp once over the ranks (each adds da' eA of its partial eA)
     const double lam_dpg = d->dpg_lambda ? lambda : 0.0;
-    if (!folded) {
+    TRY_RC(launch_camera_update(d, gc, lam_dpg, folded));
+    if (d->fused) {
         KT_B(d);
-        if (const int rc = launch_camera_update(d, gc, lam_dpg)) return rc;
-        KT_E(d, KT_CAMUPD);
+        TRY_RC(launch_long_db(d, lambda));
+        const ba_upd u{d->W, d->da, d->eB, d->Vinv, d->b, d->ndb, lambda, d->db, d->b_new,
+                       d->chsse2 + 2 * (size_t)d->nch, d->seg_long, d->long_o0, d->dpg_long};
+        BA_DISPATCH(d->na, (lin_chunk_launch<NA>(d, f, d->a_new, d->rot_new, d->b_new, d->W2,
+                                                 d->V2, d->eB2, d->upart2, d->chsse2, &u)));
+        if (d->nl > 0)   // long tracks: V2 / eB2 = sum of their segments' partials
+            k_long_vsum<<<d->nl, 64, 0, d->stream>>>(d->long_pt, d->long_seg0, d->vseg, d->V2,
+                                                     d->eB2);
+        KT_E(d, KT_LIN_UPD);
+        // (the new SSE = the new linearisation's SSE)
+        return launch_final_sums(d, d->chsse2, d->chsse2 + 2 * (size_t)d->nch, gc, lam_dpg,
+                                 folded);
     }
     if (chunked) {
         KT_B(d);
-        if (d->nl > 0)   // long tracks: db, b_new, dp'g over all their observations
-            BA_DISPATCH(d->na, (k_long_db<NA><<<d->nl, 256, 0, d->stream>>>(
-                                   d->long_pt, d->long_o0, d->obs_cam, d->W, d->da, d->eB,
-                                   d->Vinv, d->b, d->ndb, lambda, d->db, d->b_new,
-                                   d->dpg_long)));
+        TRY_RC(launch_long_db(d, lambda));
         if (d->loss_kind) {
             const ba_loss ls{d->loss_kind, d->loss_scale};
             BA_DISPATCH(d->na, (k_point_update_chunk_loss<NA><<<d->nch, 256, 0, d->stream>>>(
@@ -3068,21 +2994,8 @@ int ba_launch_update(ba_dev *d, double lambda, ba_flags f)
                                    d->dpg_long)));
         }
         KT_E(d, KT_PTUPD);
-        // new SSE, point dpg, camera dpg: one launch
-        ba_sum3 s3 = {{d->chsse + d->nch, d->chsse + 2 * (size_t)d->nch, d->part},
-                      {d->nch, d->nch, gc},
-                      {d->scal + 1, d->scal + 3, d->scal + 2},
-                      d->scal, nullptr, 0.0, d->pub_cnt};
-        if (folded) sum3_camera_dpg(d, lam_dpg, &s3);
-        if (d->publish_req) {
-            d->seq++;
-            s3.hres = d->hres_dev;
-            s3.seq = (double)d->seq;
-            d->publish_req = 0;
-            d->published = 1;
-        }
-        k_sum_parts3<<<3, 1024, 0, d->stream>>>(s3);
-        return -(int)hipGetLastError();
+        return launch_final_sums(d, d->chsse + d->nch, d->chsse + 2 * (size_t)d->nch, gc,
+                                 lam_dpg, folded);
     }
     k_sum_parts<<<1, BA_SUM_BS, 0, d->stream>>>(d->part, gc, d->scal + 2);
     const int g = grid_for(d->n, 256, PT_GRID_CAP);

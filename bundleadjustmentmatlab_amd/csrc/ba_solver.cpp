@@ -941,7 +941,6 @@ static int ctx_create(const vlgba_problem *p, const vlgba_options *o, vlgba_ctx 
         c->on_pass = o->on_pass;
         c->on_pass_user = o->on_pass_user;
         c->d.no_mfma = o->schur_kernel == 1;
-        c->d.fuse_camred = BA_FUSE_CAMRED;
         c->d.ndb = o->semantics == 1 ? p->num_a : 6;
         c->d.loss_kind = VLGBA_LOSS_NONE;   // vlgba_set_loss
         c->d.loss_scale = 0.0;
@@ -1265,7 +1264,7 @@ static int lm_pass(vlgba_ctx *c, int relinearize, vlgba_step_info *info)
         // accepted step swaps in the one k_camera_update built for a_new
         if (full) TRY(ba_launch_linearize(&d, c->flags));
         mark(c, 1);
-        if (!d.ordered && d.fuse_camred && d.ngrp_mf > 0) {
+        if (!d.ordered && d.ngrp_mf > 0) {
             // U / eA / old SSE: workgroups of this pass's MFMA Schur launch
             TRY(ba_launch_camera_reduce(&d, c->flags, 1));
         } else if (!d.ordered && c->world == 1 && !c->timing) {
@@ -1549,7 +1548,7 @@ int vlgba_set_params(vlgba_ctx *c, const double *a, const double *b)
     } else {
         TRY(upload(c->d.b, b + 3 * (size_t)c->p0, nb, c->d.stream));
     }
-    TRY(ba_launch_rotations(&c->d, c->d.a, c->d.rot, 1));
+    TRY(ba_launch_rotations(&c->d, c->d.a, c->d.rot));
     c->lin_valid = 0;
     static const bool tm = std::getenv("VLGBA_SETP_TIMING") != nullptr;
     const auto t0 = std::chrono::steady_clock::now();
@@ -1607,7 +1606,7 @@ int vlgba_get_linearization(vlgba_ctx *c, double *U, double *eA, double *V, doub
     // rejected step's, or the one the fused update made at an accepted step's
     // new point), else a new one
     if (!c->lin_valid) {
-        TRY(ba_launch_rotations(&d, d.a, d.rot, 1));
+        TRY(ba_launch_rotations(&d, d.a, d.rot));
         TRY(ba_launch_linearize(&d, c->flags));
     }
     if (!c->lin_valid || c->camred_due) {
@@ -2002,7 +2001,7 @@ int vlgba_set_jacobian(vlgba_ctx *c, int kind)
     c->d.jac = kind;
     // the table of the current a in the new mode's layout; a camera update the
     // last solve folded in built the other one
-    TRY(ba_launch_rotations(&c->d, c->d.a, c->d.rot, 1));
+    TRY(ba_launch_rotations(&c->d, c->d.a, c->d.rot));
     c->lin_valid = 0;
     c->d.camupd_done = 0;
     return 0;
@@ -2332,7 +2331,7 @@ static int mex1_impl(int model, int m, int n, int num_a, const double *K, const 
         if ((rc = upload(d.a, a, (size_t)d.ld, d.stream))) break;
         if ((rc = upload(d.b, b, 3 * (size_t)n, d.stream))) break;
         ba_flags f = {0, 0, 0};
-        if ((rc = ba_launch_rotations(&d, d.a, d.rot, 1))) break;
+        if ((rc = ba_launch_rotations(&d, d.a, d.rot))) break;
         if ((rc = ba_launch_linearize(&d, f))) break;
         if ((rc = ba_launch_camera_reduce(&d, f))) break;
         if ((rc = download(jr.data(), d.jrec, jr.size(), d.stream))) break;

@@ -157,6 +157,15 @@ def test_vinv_fold_bit_identical(gpu, kind, kw):
     assert on["plan"]["mfma_groups"] == on["plan"]["groups"] > 1, on["plan"]
 
 
+@pytest.mark.parametrize("n", [255, 256, 257])
+def test_vinv_fold_bit_identical_at_the_batch_edge(gpu, n):
+    """k_point_vinv's 256-point batches (the fold off) against the Schur
+    groups' prologues (the fold on), which run the same routine over their own
+    few points: a partial batch, exactly one batch, one batch and one point."""
+    on, _ = _on_off(gpu, _banded(m=30, n=n), 6, {}, "vinv")
+    assert on["plan"]["mfma_groups"] == on["plan"]["groups"] > 1, on["plan"]
+
+
 def test_vinv_fold_separate_update_kernels(gpu):
     """VLGBA_FUSED=0: k_point_update_chunk reads the folded V*^-1."""
     _on_off(gpu, _banded(), 6, {}, "vinv", extra_env={"VLGBA_FUSED": "0"})
