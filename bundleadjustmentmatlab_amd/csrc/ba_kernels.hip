@@ -54,9 +54,31 @@ extern "C" int vlgba_debug_stamps(unsigned long long *out, int reset)
     }
     return 0;
 }
+// k_schur_mfma's chunk loop, per wave (tools/schur_head_stamps.py): the cycles
+// of an iteration's four phases summed over the wave's chunks -- top -> last
+// global load issued -> first MFMA -> last MFMA -> next top --, the wave's
+// place (HW_ID, XCC_ID) and its clock at the first MFMA of chunks 8, 16, 24.
+// One record of 8 words per wave, the last launch's.  The scheduling barriers
+// keep each clock read where the source has it.
+#define BA_MFST_WG 4096
+__device__ unsigned long long g_mfst[BA_MFST_WG * 4 * 8];
+#define MF_CLK(v)                                                                   \
+    do {                                                                            \
+        __builtin_amdgcn_sched_barrier(0);                                          \
+        v = __builtin_amdgcn_s_memtime();                                           \
+        __builtin_amdgcn_sched_barrier(0);                                          \
+    } while (0)
+extern "C" int vlgba_debug_mf_stamps(unsigned long long *out, int nwords)
+{
+    const size_t nb = sizeof(unsigned long long) * (size_t)nwords;
+    if (nb > sizeof(g_mfst)) return -1;
+    if (hipMemcpyFromSymbol(out, HIP_SYMBOL(g_mfst), nb) != hipSuccess) return -1;
+    return 0;
+}
 #else
 #define STAMP_DECL
 #define STAMP(i)
+#define MF_CLK(v)
 #endif
 
 typedef double v2d __attribute__((ext_vector_type(2)));   // (for the non-temporal builtins)
@@ -1469,7 +1491,11 @@ __global__ __launch_bounds__(256, (NA == 6) ? BA_MF_WAVES : 1) void k_schur_mfma
     double *gacc = sm;                                   // [gcap][NA*NA]
     double *geacc = gacc + gcap * NA * NA;               // [ecap][NA]
     unsigned *rec = (unsigned *)(geacc + ecap * NA);     // the group's chunk records
-    __shared__ int gp0[BA_GROUP_CH + 1], gob[BA_GROUP_CH + 1], gbo[BA_GROUP_CH + 1];
+    // per chunk, at a fixed stride: first point, first observation, record
+    // offset, and  C | flags << 8 | np << 16 | direct << 24  (C, flags: the
+    // record's; direct: 20 points whose observation table is the identity, set
+    // below); entry nc closes the list
+    __shared__ int4 chd[BA_GROUP_CH + 1];
     // groups last to first: linearisation wrote W first to last (streamed past
     // the caches), so the W rows read here last are the first ones, still in
     // the Infinity Cache when k_point_update_chunk reads W first to last
@@ -1493,9 +1519,30 @@ __global__ __launch_bounds__(256, (NA == 6) ? BA_MF_WAVES : 1) void k_schur_mfma
     for (int q = tid; q < nge * NA; q += 256) geacc[q] = 0.0;
     for (int q = tid; q < nrw; q += 256) rec[q] = blob[rb0 + q];
     for (int q = tid; q <= nc; q += 256) {
-        gp0[q] = ch_pt[c0 + q];
-        gob[q] = ch_obase[c0 + q];
-        gbo[q] = ch_blob[c0 + q] - rb0;
+        const int i0 = ch_pt[c0 + q], bo = ch_blob[c0 + q] - rb0;
+        const int np = q < nc ? ch_pt[c0 + q + 1] - i0 : 0;
+        chd[q] = int4{i0, ch_obase[c0 + q], bo, np << 16};
+    }
+    __syncthreads();
+    // a chunk is direct when its table maps (point p, camera slot c) to the
+    // observation p C + c: every point sees every camera of the chunk, point
+    // after point, cameras ascending.  Its fragment offsets then need no table.
+    // The record's own dense flag (fl & 1) says only that no view is missing,
+    // not that the chunk is full nor in which order a point's observations are
+    // stored (a reordered plan's need not ascend): the table itself is compared
+    for (int q = tid; q < nc; q += 256) {
+        const unsigned *r = rec + chd[q].z;
+        const unsigned h1 = r[1];
+        const int C = (int)(h1 & 0xffu), np = chd[q].w >> 16;
+        unsigned bad = np == BA_MF_PTS ? 0u : 1u;
+        if (!bad) {
+            const unsigned *tw = r + 2 + C + C * (C + 1) / 2;   // BA_MF_PTS C / 4 whole words
+            for (int c = 0; c < C; c++)
+#pragma unroll
+                for (int w = BA_MF_PTS / 4 * c; w < BA_MF_PTS / 4 * (c + 1); w++)
+                    bad |= tw[w] ^ (0x03020100u + 0x04040404u * (unsigned)w);
+        }
+        chd[q].w |= (int)(h1 & 0xffffu) | (bad ? 0 : 1 << 24);
     }
     __syncthreads();
     // lane constants: K rows of its fragments, slab columns of its tiles
@@ -1514,31 +1561,18 @@ __global__ __launch_bounds__(256, (NA == 6) ? BA_MF_WAVES : 1) void k_schur_mfma
     // li >= 9: eB[lk] of point 5w + 4 -- which process() broadcasts along the
     // row; v4: the s = 3 Y MFMA's A fragment V*^-1[lk][li] of point 5w + 4
     // (zero outside rows li < 3, K lk < 3)
-    auto load = [&](int k, double (&wf)[4][RT], double &vg, double &v4) {
-        const unsigned *r = rec + gbo[k];
-        const int np = gp0[k + 1] - gp0[k], i0 = gp0[k], ob = gob[k];
-        const int C = (int)(r[1] & 0xffu);
-        const unsigned char *tab = (const unsigned char *)(r + 2 + C + C * (C + 1) / 2);
+    auto load = [&](int i0, int ob, int bo, unsigned hw, double (&wf)[4][RT], double &vg,
+                    double &v4) {
+        const int C = (int)(hw & 0xffu), np = (int)((hw >> 16) & 0xffu);
         const double *wbase = W + (size_t)WS * ob;
         const double *vbase = Vinv + 9 * (size_t)i0;
         const double *ebase = eB + 3 * (size_t)i0;
         const int wz = WS * (nobs_all - ob), vz = 9 * (n_all - i0), ez = 3 * (n_all - i0);
-        // one lane offset per (point, column tile) -- the zero row's when absent;
-        // the components are immediate offsets from it (zero row: 3 NA doubles)
         const int pA = BA_MF_KB * wv + lk, p4 = BA_MF_KB * wv + 4;
         const bool pvA = pA < np, pv4 = lk < 3 && p4 < np;
-#pragma unroll
-        for (int t = 0; t < RT; t++) {
-            const bool cvA = pvA && ccs[t] < C, cv4 = pv4 && ccs[t] < C;
-            const int iA = tab[cvA ? pA * C + ccs[t] : 0];   // clamped read, no branch
-            const int i4 = tab[cv4 ? p4 * C + ccs[t] : 0];
-            const int oA = (cvA && iA != 0xff ? WS * iA : wz) + crr[t];
-            const int o4 = (cv4 && i4 != 0xff ? WS * i4 + NA * lk : wz) + crr[t];
-#pragma unroll
-            for (int s = 0; s < 3; s++) wf[s][t] = wbase[oA + NA * s];
-            wf[3][t] = wbase[o4];
-        }
-        // V*^-1 entries (0,0) (1,0) (2,0) (1,1) (2,1) (2,2) -> lanes 0..5
+        // vg and v4 first: process() needs them first, and their addresses
+        // need the header only.  V*^-1 entries (0,0) (1,0) (2,0) (1,1) (2,1)
+        // (2,2) -> lanes 0..5
         const int vo = li + (li >= 3 ? 1 : 0) + (li >= 5 ? 2 : 0);
         const double *src = li < 6   ? vbase + (pvA ? 9 * pA + vo : vz)
                             : li < 9 ? ebase + (pvA ? 3 * pA + li - 6 : ez)
@@ -1546,6 +1580,34 @@ __global__ __launch_bounds__(256, (NA == 6) ? BA_MF_WAVES : 1) void k_schur_mfma
         vg = *src;
         const bool dv = p4 < np && li < 3 && lk < 3;
         v4 = vbase[dv ? 9 * p4 + lk + 3 * li : vz];
+        // one lane offset per (point, column tile) -- the zero row's when absent;
+        // the components are immediate offsets from it (zero row: 3 NA doubles)
+        int oA[RT], o4[RT];
+        if (hw >> 24) {   // (uniform) direct: observation p C + c, every point present
+#pragma unroll
+            for (int t = 0; t < RT; t++) {
+                const bool cv = ccs[t] < C;
+                oA[t] = (cv ? WS * (pA * C + ccs[t]) : wz) + crr[t];
+                o4[t] = (cv && lk < 3 ? WS * (p4 * C + ccs[t]) + NA * lk : wz) + crr[t];
+            }
+        } else {
+            const unsigned *r = rec + bo;
+            const unsigned char *tab = (const unsigned char *)(r + 2 + C + C * (C + 1) / 2);
+#pragma unroll
+            for (int t = 0; t < RT; t++) {
+                const bool cvA = pvA && ccs[t] < C, cv4 = pv4 && ccs[t] < C;
+                const int iA = tab[cvA ? pA * C + ccs[t] : 0];   // clamped read, no branch
+                const int i4 = tab[cv4 ? p4 * C + ccs[t] : 0];
+                oA[t] = (cvA && iA != 0xff ? WS * iA : wz) + crr[t];
+                o4[t] = (cv4 && i4 != 0xff ? WS * i4 + NA * lk : wz) + crr[t];
+            }
+        }
+#pragma unroll
+        for (int t = 0; t < RT; t++) {
+#pragma unroll
+            for (int s = 0; s < 3; s++) wf[s][t] = wbase[oA[t] + NA * s];
+            wf[3][t] = wbase[o4[t]];
+        }
     };
     d4 accS[NTL];
     double eacc[RT];
@@ -1553,17 +1615,19 @@ __global__ __launch_bounds__(256, (NA == 6) ? BA_MF_WAVES : 1) void k_schur_mfma
     for (int u = 0; u < NTL; u++) accS[u] = d4{0.0, 0.0, 0.0, 0.0};
 #pragma unroll
     for (int t = 0; t < RT; t++) eacc[t] = 0.0;
+#ifdef BA_STAMPS
+    unsigned long long st_ph[4] = {0, 0, 0, 0}, st_fm[3] = {0, 0, 0}, st_t0, st_t1, st_t2, st_t3;
+#endif
     // one chunk: Y tiles, e_ sums, lower S tiles; flush at a change of cameras
-    auto process = [&](int k, const double (&wc)[4][RT], double vg, double v4) {
+    auto process = [&](int bo, unsigned hw, const double (&wc)[4][RT], double vg, double v4) {
         // the row's entries from its lanes 0..9: V*^-1 of the lane's own point
         // (the six entries in load()'s order) and the eB of its four K steps
         const double vc[6] = {row16_bcast_c<0>(vg), row16_bcast_c<1>(vg), row16_bcast_c<2>(vg),
                               row16_bcast_c<3>(vg), row16_bcast_c<4>(vg), row16_bcast_c<5>(vg)};
         const double ec[4] = {row16_bcast_c<6>(vg), row16_bcast_c<7>(vg), row16_bcast_c<8>(vg),
                               row16_bcast_c<9>(vg)};
-        const unsigned *r = rec + gbo[k];
-        const unsigned h1 = r[1];
-        const int C = (int)(h1 & 0xffu), fl = (int)((h1 >> 8) & 0xffu), Rc = NA * C;
+        const unsigned *r = rec + bo;
+        const int C = (int)(hw & 0xffu), fl = (int)((hw >> 8) & 0xffu), Rc = NA * C;
         // row tile by row tile: one Y tile live at a time.  Every tile runs (tiles
         // past the chunk's columns multiply exact zeros): no branch between the
         // next chunk's loads and the MFMAs, so their waits stay precise
@@ -1575,6 +1639,7 @@ __global__ __launch_bounds__(256, (NA == 6) ? BA_MF_WAVES : 1) void k_schur_mfma
         // was), at a sixth of its matrix-pipe time
         double y4[RT];
         const double va = row4_bcast(v4, 0);
+        MF_CLK(st_t2);
 #pragma unroll
         for (int ti = 0; ti < RT; ti++)
             y4[ti] = __builtin_amdgcn_mfma_f64_4x4x4f64(va, wc[3][ti], 0.0, 0, 0, 0);
@@ -1601,14 +1666,19 @@ __global__ __launch_bounds__(256, (NA == 6) ? BA_MF_WAVES : 1) void k_schur_mfma
 #pragma unroll
                     for (int rg = 0; rg < 4; rg++) {
                         if (16 * ti + 4 * rg >= Rc) continue;   // (uniform) rows past the chunk
+                        // the four K steps' swizzles together, one LDS latency
+                        // for the group of rows
+                        double ya[4];
+#pragma unroll
+                        for (int s = 0; s < 4; s++) ya[s] = row4_bcast(y[s], rg);
+                        __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
                         for (int s = 0; s < 4; s++) {
-                            const double ya = row4_bcast(y[s], rg);
 #pragma unroll
                             for (int tj = 0; tj <= ti; tj++) {
                                 d4 &t = accS[ti * (ti + 1) / 2 + tj];
-                                t[rg] = __builtin_amdgcn_mfma_f64_4x4x4f64(ya, wc[s][tj], t[rg], 0,
-                                                                           0, 0);
+                                t[rg] = __builtin_amdgcn_mfma_f64_4x4x4f64(ya[s], wc[s][tj], t[rg],
+                                                                           0, 0, 0);
                             }
                         }
                     }
@@ -1623,6 +1693,7 @@ __global__ __launch_bounds__(256, (NA == 6) ? BA_MF_WAVES : 1) void k_schur_mfma
                 }
             }
         }
+        MF_CLK(st_t3);
         if (fl & 2) {   // flush: wave by wave into the group accumulators
             const unsigned *ge = r + 2;
             const unsigned *pair = ge + C;
@@ -1634,36 +1705,67 @@ __global__ __launch_bounds__(256, (NA == 6) ? BA_MF_WAVES : 1) void k_schur_mfma
                 ecol[t] = ((v0 + v1) + v2) + v3;
                 eacc[t] = 0.0;
             }
+            // every wave first finds the accumulator entry of each of its tile
+            // elements ahead of its turn (the pair reads come out one after
+            // another, each waited for, but in all four waves at once), so that
+            // a turn is a batch of reads, the adds and the writes per tile: the
+            // turns are what the four waves cannot overlap.
+            // A wave's entries are distinct (one (row, column) each), so the
+            // batch adds what an element-by-element loop adds, to the same sums
+            // in the same wave order.  gp: the entry's LDS address (entry 0
+            // where the element has none: read, never written), gm: the
+            // elements that have one.  fi, fk: li, lk, opaque to the optimiser,
+            // so that the flush's lane constants are formed here and hold no
+            // registers through the chunk loop
+            int fi = li, fk = lk;
+            asm volatile("" : "+v"(fi), "+v"(fk));
+            lds_double *gp[NTL][4], *ep[RT];
+            unsigned gm[(4 * NTL + 31) / 32] = {};
+#pragma unroll
+            for (int ti = 0; ti < RT; ti++)
+#pragma unroll
+                for (int tj = 0; tj <= ti; tj++) {
+                    const int col = 16 * tj + fi;
+#pragma unroll
+                    for (int q = 0; q < 4; q++) {
+                        const int u = ti * (ti + 1) / 2 + tj;
+                        const int rr = 16 * ti + fk + 4 * q;
+                        const bool in = rr < Rc && col < Rc && rr >= col;
+                        const int cr = rr / NA, cc = col / NA;
+                        const unsigned gsl = pair[in ? cr * (cr + 1) / 2 + cc : 0];   // clamped
+                        const bool ok = in && gsl != 0xffffffffu;
+                        gp[u][q] = (lds_double *)gacc +
+                                   (ok ? (int)gsl * (NA * NA) + (rr - NA * cr) + NA * (col - NA * cc)
+                                       : 0);
+                        gm[(4 * u + q) >> 5] |= ok ? 1u << ((4 * u + q) & 31) : 0u;
+                    }
+                }
+#pragma unroll
+            for (int t = 0; t < RT; t++) {
+                const int col = 16 * t + fi;
+                const bool ok = fk == 0 && col < Rc;
+                const int cs = col / NA;
+                const unsigned gel = ge[ok ? cs : 0];   // clamped
+                ep[t] = (lds_double *)geacc + (ok ? (int)gel * NA + col - NA * cs : 0);
+            }
             for (int w = 0; w < 4; w++) {
                 if (wv == w) {
 #pragma unroll
-                    for (int ti = 0; ti < RT; ti++)
+                    for (int u = 0; u < NTL; u++) {
+                        double gv[4];
 #pragma unroll
-                        for (int tj = 0; tj <= ti; tj++) {
-                            const int col = 16 * tj + li;
+                        for (int q = 0; q < 4; q++) gv[q] = *gp[u][q];
 #pragma unroll
-                            for (int q = 0; q < 4; q++) {
-                                const int rr = 16 * ti + lk + 4 * q;
-                                if (rr < Rc && col < Rc && rr >= col) {
-                                    const int cr = rr / NA, cc = col / NA;
-                                    const unsigned gsl = pair[cr * (cr + 1) / 2 + cc];
-                                    if (gsl != 0xffffffffu)
-                                        gacc[gsl * (NA * NA) + (rr - NA * cr) +
-                                             NA * (col - NA * cc)] +=
-                                            accS[ti * (ti + 1) / 2 + tj][q];
-                                }
-                            }
-                        }
-                    if (lk == 0) {
-#pragma unroll
-                        for (int t = 0; t < RT; t++) {
-                            const int col = 16 * t + li;
-                            if (col < Rc) {
-                                const int cs = col / NA;
-                                geacc[ge[cs] * NA + col - NA * cs] += ecol[t];
-                            }
-                        }
+                        for (int q = 0; q < 4; q++)
+                            if (gm[(4 * u + q) >> 5] >> ((4 * u + q) & 31) & 1u)
+                                *gp[u][q] = gv[q] + accS[u][q];
                     }
+                    double ev[RT];
+#pragma unroll
+                    for (int t = 0; t < RT; t++) ev[t] = *ep[t];
+#pragma unroll
+                    for (int t = 0; t < RT; t++)
+                        if (fk == 0 && 16 * t + fi < Rc) *ep[t] = ev[t] + ecol[t];
                 }
                 __syncthreads();
             }
@@ -1675,10 +1777,56 @@ __global__ __launch_bounds__(256, (NA == 6) ? BA_MF_WAVES : 1) void k_schur_mfma
     // chunk's loads (a second, software-pipelined register set was tried and
     // never became the default)
     double wa[4][RT], vg, v4;
+    // the header is uniform: scalars, so that the chunk's bases and the
+    // direct / table choice are formed on the scalar unit (the loads
+    // themselves still take 64-bit vector addresses: the compiler adds base and
+    // lane offset per load).  Chunk k + 1's header is read behind chunk k's
+    // loads and waited for ahead of chunk k's first MFMA: its LDS round trip
+    // lies under the loads' latency, not at the top of the next iteration
+    auto header = [&](int k, int &i0, int &ob, int &bo, unsigned &hw) {
+        const int4 h = chd[k];
+        i0 = __builtin_amdgcn_readfirstlane(h.x);
+        ob = __builtin_amdgcn_readfirstlane(h.y);
+        bo = __builtin_amdgcn_readfirstlane(h.z);
+        hw = (unsigned)__builtin_amdgcn_readfirstlane(h.w);
+    };
+    int hi0, hob, hbo;
+    unsigned hhw;
+    header(0, hi0, hob, hbo, hhw);
+    MF_CLK(st_t0);
     for (int k = 0; k < nc; k++) {
-        load(k, wa, vg, v4);
-        process(k, wa, vg, v4);
+        load(hi0, hob, hbo, hhw, wa, vg, v4);
+        MF_CLK(st_t1);
+        const int cbo = hbo;
+        const unsigned chw = hhw;
+        header(k + 1, hi0, hob, hbo, hhw);
+        process(cbo, chw, wa, vg, v4);
+#ifdef BA_STAMPS
+        unsigned long long st_t4;
+        MF_CLK(st_t4);
+        st_ph[0] += st_t1 - st_t0;
+        st_ph[1] += st_t2 - st_t1;
+        st_ph[2] += st_t3 - st_t2;
+        st_ph[3] += st_t4 - st_t3;
+        if (k == 8) st_fm[0] = st_t2;
+        if (k == 16) st_fm[1] = st_t2;
+        if (k == 24) st_fm[2] = st_t2;
+        st_t0 = st_t4;
+#endif
     }
+#ifdef BA_STAMPS
+    if (lane == 0 && blockIdx.x < BA_MFST_WG) {
+        unsigned long long *o = g_mfst + 8 * (4 * (size_t)blockIdx.x + wv);
+#pragma unroll
+        for (int q = 0; q < 4; q++) o[q] = st_ph[q];
+        // HW_REG_HW_ID (4) and HW_REG_XCC_ID (20), all 32 bits; chunks in the high half
+        o[4] = (unsigned long long)__builtin_amdgcn_s_getreg(4 | (31 << 11)) |
+               ((unsigned long long)__builtin_amdgcn_s_getreg(20 | (31 << 11)) << 32);
+#pragma unroll
+        for (int q = 0; q < 3; q++) o[5 + q] = st_fm[q];
+        o[4] |= (unsigned long long)(nc & 0xff) << 56;
+    }
+#endif
     __syncthreads();
     for (int q = tid; q < ngs * NA * NA; q += 256) spart[(size_t)NA * NA * gs0 + q] = gacc[q];
     for (int q = tid; q < nge * NA; q += 256) epart[(size_t)NA * ge0 + q] = geacc[q];
