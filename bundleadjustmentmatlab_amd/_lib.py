@@ -139,7 +139,7 @@ SIGNATURES = {
 }
 
 ERRORS = {-1001: "bad argument",
-          -1002: "num_a must be 6, 7 or 10 (Euclidean) or 12 (projective)",
+          -1002: "num_a must be 6, 7, 9 or 10 (Euclidean) or 12 (projective)",
           -1003: "duplicate (point, camera) observation", -1004: "out of host memory",
           -1005: "RCCL communicator failure",
           -1006: "library / header ABI mismatch",

@@ -111,13 +111,23 @@ def parse_options(m, n, varargin, x=None, nomex=False):
     return o
 
 
-def pack_a(K, Te, w, nvk):
-    """a = [w; T; (K)] (bundle_euclid.m:89-96)."""
+RADIAL_NVK = 3   # the radial model's variable calibration: a[6:9] = f, k1, k2
+
+
+def pack_a(K, Te, w, nvk, kd=None):
+    """a = [w; T; (K)] (bundle_euclid.m:89-96); the radial model (nvk =
+    RADIAL_NVK, kd 2 x m): a = [w; T; f; k1; k2] with f = K[0]."""
     m = w.shape[1]
     a = np.zeros((6 + nvk, m), order="F")
     a[0:3] = w
     a[3:6] = Te
-    if nvk == 1:
+    if nvk == RADIAL_NVK:
+        kd = np.asarray(kd, dtype=np.float64)
+        if kd.shape != (2, m):
+            raise ValueError(f"radial: expected 2 x {m} coefficients, got {kd.shape}")
+        a[6] = K[0]
+        a[7:9] = kd
+    elif nvk == 1:
         a[6] = K[0]
     elif nvk == 4:
         a[6:10] = K
@@ -127,7 +137,7 @@ def pack_a(K, Te, w, nvk):
 def unpack(K, a, b, Xe4, nvk):
     """bundle_euclid.m:255-267 (Xe_(4,:) is the input Xe(4,:), App. A Q5)."""
     K_ = np.array(K, dtype=np.float64, order="F")
-    if nvk == 1:
+    if nvk == 1 or nvk == RADIAL_NVK:   # (radial: a[7:9] = k1, k2 are the caller's)
         K_[0] = a[6]
         K_[1] = a[6]
     elif nvk == 4:
@@ -189,8 +199,13 @@ class BundleAdjuster:
     """One problem resident on one GPU (vlgba_ctx).
 
     obs_pt / obs_cam (0-based) and obs_x (N, 2) describe the visible
-    observations; K is 4 x m; num_a is 6 (fix_calibration), 7 (fix_principal)
-    or 10 (variable K).  Options follow bundle_euclid.m's names.  ``solver``
+    observations; K is 4 x m; num_a is 6 (fix_calibration), 7 (fix_principal),
+    10 (variable K) or 9: the camera with radial distortion, a = [w; T; f; k1;
+    k2] per camera, x = f d n + (K[2], K[3]) with n the normalised image point
+    and d = 1 + k1 |n|^2 + k2 |n|^4.  That model has analytic Jacobians only
+    (jacobian="fd" raises VlgbaError -1001), always takes all nine rows of da
+    into the back substitution, and does not go with ``parity`` / ``ordered``
+    (VlgbaError -1001 at creation).  Options follow bundle_euclid.m's names.  ``solver``
     picks the reduced-camera solve: "auto" (cyclic reduction when S is
     tile-tridiagonal, else envelope Cholesky -- on a nested-dissection camera
     order when that shortens its chain of steps), "envelope", "nd" (the
@@ -563,13 +578,16 @@ class BundleAdjuster:
 # ---------------------------------------------------------------------------
 def euclid_obs_adjuster(K, m, n, obs_pt, obs_cam, obs_x, *varargin, num_vis=0.0, device=0,
                         rank=0, world_size=1, comm_id=None, semantics="mex", loss="none",
-                        loss_scale=0.0, jacobian=None, **solver):
+                        loss_scale=0.0, jacobian=None, radial=False, **solver):
     """The BundleAdjuster that bundle_euclid_obs would create for this problem
-    and these options (its structure only: no parameter values), so a caller
+    and these options (its structure only: no parameter values; ``radial``:
+    the num_a = 9 model, whatever the calibration options say), so a caller
     can build it ahead of time -- the host plan of vlgba_create runs with the
     GIL released (ctypes), e.g. on a worker thread while the previous solve
     runs (incremental.py) -- and hand it to bundle_euclid_obs(adjuster=...)."""
     o = parse_options(m, n, varargin, nomex=semantics == "nomex")
+    if radial:
+        o["num_variableK"] = RADIAL_NVK
     ba = BundleAdjuster(K, obs_pt, obs_cam, obs_x, n, 6 + o["num_variableK"],
                         fix_structure=o["fix_structure"], fix_motion=o["fix_motion"],
                         pivot=o["pivot"] if o["fix_pivot"] else None, verbose=o["verbose"],
@@ -615,8 +633,14 @@ def _adjuster_fingerprint(K, m, n, obs_pt, obs_cam, obs_x, o, num_vis, semantics
 def bundle_euclid_obs(K, Te, w, Xe, obs_pt, obs_cam, obs_x, *varargin, num_vis=0.0, device=0,
                       rank=0, world_size=1, comm_id=None, return_stats=False,
                       semantics="mex", adjuster=None, return_covariance=False, loss="none",
-                      loss_scale=0.0, jacobian=None, covariance_method=None, **solver):
+                      loss_scale=0.0, jacobian=None, covariance_method=None, radial=None,
+                      **solver):
     """bundle_euclid on a COO observation list (0-based point / camera ids).
+    ``radial``: 2 x m initial radial coefficients (k1; k2) -- the solve then
+    refines a = [w; T; f; k1; k2] per camera (num_a = 9, f from K(1,:), the
+    principal point fixed, whatever 'fix_calibration' / 'fix_principal' say)
+    with analytic Jacobians, and the refined 2 x m coefficients are returned as
+    an extra last output.
     ``jacobian``: "fd", "analytic" or None (BundleAdjuster); a prebuilt adjuster
     must have been made in the mode asked for here (None: its own).
     ``loss`` / ``loss_scale``: the robust loss (BundleAdjuster); error_ is then
@@ -632,9 +656,12 @@ def bundle_euclid_obs(K, Te, w, Xe, obs_pt, obs_cam, obs_x, *varargin, num_vis=0
     m, n = w.shape[1], Xe.shape[1]
     nomex = semantics == "nomex"
     o = parse_options(m, n, varargin, nomex=nomex)
+    if radial is not None:
+        if jacobian == "fd":
+            raise ValueError("radial distortion has analytic Jacobians only")
+        o["num_variableK"] = RADIAL_NVK
     nvk = o["num_variableK"]
-    num_a = 6 + nvk
-    a = pack_a(K, Te, w, nvk)
+    a = pack_a(K, Te, w, nvk, radial)
     b = _F(Xe[0:3])
     if adjuster is not None:
         if solver:
@@ -652,7 +679,8 @@ def bundle_euclid_obs(K, Te, w, Xe, obs_pt, obs_cam, obs_x, *varargin, num_vis=0
         ba = euclid_obs_adjuster(K, m, n, obs_pt, obs_cam, obs_x, *varargin, num_vis=num_vis,
                                  device=device, rank=rank, world_size=world_size,
                                  comm_id=comm_id, semantics=semantics, loss=loss,
-                                 loss_scale=loss_scale, jacobian=jacobian, **solver)
+                                 loss_scale=loss_scale, jacobian=jacobian,
+                                 radial=radial is not None, **solver)
     with ba:
         ba.set_params(a, b)
         err, st = ba.run()
@@ -663,7 +691,8 @@ def bundle_euclid_obs(K, Te, w, Xe, obs_pt, obs_cam, obs_x, *varargin, num_vis=0
     # Xe_(4,:): the input's (bundle_euclid.m:267) or ones (bundle_euclid_nomex.m:364)
     out = unpack(K, a, b, np.ones((1, n)) if nomex else Xe[3:4], nvk) + (err,)
     out = out + (st,) if return_stats else out
-    return out + (cov,) if return_covariance else out
+    out = out + (cov,) if return_covariance else out
+    return out + (a[7:9].copy(order="F"),) if radial is not None else out
 
 
 def bundle_euclid(K, Te, w, Xe, x, *varargin, device=0, return_stats=False, semantics="mex",
@@ -671,7 +700,8 @@ def bundle_euclid(K, Te, w, Xe, x, *varargin, device=0, return_stats=False, sema
                   **solver):
     """[K_ Te_ w_ Xe_ error_] = bundle_euclid(K, Te, w, Xe, x, ...)  (bundle_euclid.m:1);
     ``loss`` / ``loss_scale``, ``covariance_method`` and ``jacobian="fd" |
-    "analytic"`` (one of the solver keywords) as bundle_euclid_obs."""
+    "analytic"`` and ``radial=kd0`` (among the solver keywords) as
+    bundle_euclid_obs."""
     x = _F(x)
     m, n = np.shape(w)[1], x.shape[1]
     o = parse_options(m, n, varargin, x=x, nomex=semantics == "nomex")

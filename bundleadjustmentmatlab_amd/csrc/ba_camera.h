@@ -12,7 +12,8 @@
 // camera j as the projections see it.  Euclidean (NA = 6 / 7 / 10): a0, the
 // calibration of reproject_point.h:26-41 and the hoisted rotations
 // R(w), R(w + h e_k), R(w + 0) (k_rotations); projective (NA = BA_PROJ_NA):
-// P = a0 (mex_bundle_proj_1_XABeUVWeAeB.c:21-22), K4 / rot unused.
+// P = a0 (mex_bundle_proj_1_XABeUVWeAeB.c:21-22), K4 / rot unused; radial
+// distortion (NA = BA_RAD_NA): a0, the principal point and R(w), dR/dw_k.
 //   project(b, x)         x = proj(a0, b)
 //   project_dcam(k, b, x) x = proj(a0 + h e_k, b), a1 formed component-wise
 //                         as a0 + h * da (mex_bundle_1 :30-33, proj :47-51)
@@ -131,6 +132,106 @@ struct cam_view<NA, false> {
     }
     static __device__ __forceinline__ constexpr bool jac_lane1(int col) { return col >= 3; }
 };
+
+// Radial-distortion camera (NA = BA_RAD_NA: a = [w; T; f; k1; k2], principal
+// point K4[2], K4[3] fixed; vlg_project_radial).  Analytic Jacobians only: the
+// context is created in that mode and cannot leave it, so the table's slots
+// 1..3 always hold dR/dw_k.  The forward-difference members exist because the
+// FD kernels are instantiated for every NA; no host path launches them at this
+// NA, and they return the base projection.
+template <>
+struct cam_view<BA_RAD_NA, false> {
+    static constexpr int NA = BA_RAD_NA;
+    double a0[NA], c2[2], Rl[9];
+    const double *R;
+    __device__ __forceinline__ cam_view(const double *__restrict__ a,
+                                        const double *__restrict__ K4,
+                                        const double *__restrict__ rot, int j)
+        : cam_view(a, K4, rot, j, j)
+    {
+    }
+    __device__ __forceinline__ cam_view(const double *__restrict__ a,
+                                        const double *__restrict__ K4,
+                                        const double *__restrict__ rot, int jr, int j)
+    {
+#pragma unroll
+        for (int c = 0; c < NA; c++) a0[c] = a[(size_t)NA * j + c];
+        c2[0] = K4[4 * (size_t)j + 2];
+        c2[1] = K4[4 * (size_t)j + 3];
+        R = rot + 45 * (size_t)jr;
+#pragma unroll
+        for (int q = 0; q < 9; q++) Rl[q] = R[q];
+    }
+    __device__ __forceinline__ void project(const double b[3], double x[2]) const
+    {
+        vlg_project_radial(a0 + 6, c2, Rl, a0 + 3, b, x);
+    }
+    __device__ __forceinline__ void project_dcam(int, const double b[3], double x[2]) const
+    {
+        project(b, x);
+    }
+    __device__ __forceinline__ void project_col(int, const double b[3], double x[2]) const
+    {
+        project(b, x);
+    }
+    // With n = (u, v), r2, d of the projection (vlg_radial_n), g = 2 k1 +
+    // 4 k2 r2:  Jn = dx/dn = f (d I + g n n'),  Jx = dx/dXc = Jn (1/z) [I | -n].
+    // For a direction D of Xc, p = (D0 - u D2, D1 - v D2) / z and
+    //   Jx D = (f d) p + (f g) (n'p) n.
+    // A_wk = Jx (dR_k b), A_T = Jx, dx/df = d n, dx/dk1 = f r2 n, dx/dk2 =
+    // f r2^2 n, B = Jx R.  Lane 0 forms the rotation columns (three 3 x 3
+    // products from the table), lane 1 the other nine, which need none
+    // (jac_lane1): about the same arithmetic on each.
+    __device__ __forceinline__ void jac_columns(const double b[3], int half, double *row) const
+    {
+        double n[2], iz, r2, d;
+        vlg_radial_n(a0 + 6, Rl, a0 + 3, b, n, &iz, &r2, &d);
+        const double f = a0[6], u = n[0], v = n[1];
+        const double g = 2.0 * a0[7] + 4.0 * (a0[8] * r2);
+        const double fd = f * d, fgu = (f * g) * u, fgv = (f * g) * v;
+        auto col = [&](double p0, double p1, double *o) {
+            const double s = u * p0 + v * p1;
+            o[0] = fd * p0 + fgu * s;
+            o[1] = fd * p1 + fgv * s;
+        };
+        if (!half) {
+#pragma unroll
+            for (int k = 0; k < 3; k++) {
+                const double *D = R + 9 * (1 + k);
+                double dd[3];
+                vlg_rot_b(D, b, dd);
+                col(iz * (dd[0] - u * dd[2]), iz * (dd[1] - v * dd[2]), row + 2 * k);
+            }
+        } else {
+            col(iz, 0.0, row + 6);
+            col(0.0, iz, row + 8);
+            col(-(iz * u), -(iz * v), row + 10);
+            const double fr = f * r2, frr = fr * r2;
+            row[12] = d * u;    row[13] = d * v;
+            row[14] = fr * u;   row[15] = fr * v;
+            row[16] = frr * u;  row[17] = frr * v;
+#pragma unroll
+            for (int k = 0; k < 3; k++)
+                col(iz * (Rl[3 * k] - u * Rl[3 * k + 2]), iz * (Rl[3 * k + 1] - v * Rl[3 * k + 2]),
+                    row + 2 * NA + 2 * k);
+        }
+    }
+    static __device__ __forceinline__ constexpr bool jac_lane1(int col) { return col >= 3; }
+};
+
+// the point-update kernels' new projection at this model: camera j's
+// parameters an (of a_new) and R(w) of its rot_new row
+__device__ __forceinline__ void project_radial_new(const double an[BA_RAD_NA],
+                                                   const double *__restrict__ K4,
+                                                   const double *__restrict__ rot_new, int j,
+                                                   const double b[3], double xh[2])
+{
+    double R[9];
+    const double c2[2] = {K4[4 * (size_t)j + 2], K4[4 * (size_t)j + 3]};
+#pragma unroll
+    for (int q = 0; q < 9; q++) R[q] = rot_new[45 * (size_t)j + q];
+    vlg_project_radial(an + 6, c2, R, an + 3, b, xh);
+}
 
 template <int NA>
 struct cam_view<NA, true> {

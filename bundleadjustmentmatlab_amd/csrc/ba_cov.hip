@@ -397,6 +397,7 @@ int ba_launch_point_cov(ba_dev *d, const int *list, int n8, int n64, int nwg, in
     switch (d->na) {
     case 6: return point_cov_src<6>(d, list, n8, n64, nwg, tmax, *src, out);
     case 7: return point_cov_src<7>(d, list, n8, n64, nwg, tmax, *src, out);
+    case BA_RAD_NA: return point_cov_src<BA_RAD_NA>(d, list, n8, n64, nwg, tmax, *src, out);
     case 10: return point_cov_src<10>(d, list, n8, n64, nwg, tmax, *src, out);
     case BA_PROJ_NA: return point_cov_src<BA_PROJ_NA>(d, list, n8, n64, nwg, tmax, *src, out);
     default: return -1000;

@@ -2,8 +2,9 @@
 //
 // One ba_dev per (problem, GPU).  Everything lives in HBM for the whole solve;
 // only scalars cross PCIe per LM iteration.  Layout (N = visible observations,
-// NA = num_a = 6 / 7 / 10 Euclidean camera parameters or 12 for the projective
-// camera P(:) of bundle_projective.m, m cameras, n points):
+// NA = num_a = 6 / 7 / 10 Euclidean camera parameters, 9 with radial distortion,
+// or 12 for the projective camera P(:) of bundle_projective.m, m cameras, n
+// points):
 //
 //   observations, point-major (points ascending, cameras ascending inside a
 //   point = the reference's column-major (i + n*j) visiting order per point):
@@ -62,6 +63,9 @@ void kt_end(struct ba_ktimer *t, hipStream_t s, int kid);
 // bundle_projective.m:70-73, projection mex_bundle_proj_1_XABeUVWeAeB.c:13-32;
 // no K, no rotations); NA = 6 / 7 / 10 the Euclidean [w; T; (K)]
 #define BA_PROJ_NA 12
+// NA == BA_RAD_NA: the Euclidean camera with radial distortion, a = [w; T; f;
+// k1; k2] (vlg_project_radial; analytic Jacobians only, fast path only)
+#define BA_RAD_NA 9
 
 struct ba_flags {
     int fix_structure;  // V, W, eB = 0       (bundle_euclid.m:140-144)

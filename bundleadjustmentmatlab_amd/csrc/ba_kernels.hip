@@ -1,6 +1,8 @@
 // ba_kernels.hip -- gfx950 kernels of one LM iteration (fp64), Euclidean
 // (NA = 6 / 7 / 10) and projective (NA = BA_PROJ_NA = 12: the camera is P(:),
-// mex_bundle_proj_{1,3}*.c -- the same loops with reproject_projective_point).
+// mex_bundle_proj_{1,3}*.c -- the same loops with reproject_projective_point);
+// NA = BA_RAD_NA = 9: the Euclidean camera with radial distortion (analytic
+// Jacobians, fast path only: its FD / ordered instantiations are never launched).
 //
 // Reference path (toolbox/bundle/):
 //   k_rotations        vl_rodrigues per camera, hoisted out of reproject_point.h:44
@@ -2267,6 +2269,8 @@ __global__ __launch_bounds__(256) void k_point_update(
             for (int c = 0; c < NA; c++) an[c] = a_new[(size_t)NA * j + c];
             if constexpr (NA == BA_PROJ_NA) {   // mex_bundle_proj_3_db_new.c:160-165
                 vlg_project_proj(an, bn, xh);
+            } else if constexpr (NA == BA_RAD_NA) {
+                project_radial_new(an, K4, rot_new, j, bn, xh);
             } else {
                 double k4[4], Kc[9], R[9];
 #pragma unroll
@@ -2352,6 +2356,8 @@ __device__ __forceinline__ void point_update_chunk_body(BA_PUC_ARGS, ba_loss ls)
             for (int c = 0; c < NA; c++) an[c] = a_new[(size_t)NA * j + c];
             if constexpr (NA == BA_PROJ_NA) {
                 vlg_project_proj(an, bl, xh);
+            } else if constexpr (NA == BA_RAD_NA) {
+                project_radial_new(an, K4, rot_new, j, bl, xh);
             } else {
                 double k4[4], Kc[9], R[9];
 #pragma unroll
@@ -2462,6 +2468,8 @@ __device__ __forceinline__ void point_update_chunk_body(BA_PUC_ARGS, ba_loss ls)
         for (int c = 0; c < NA; c++) an[c] = a_new[(size_t)NA * j + c];
         if constexpr (NA == BA_PROJ_NA) {   // mex_bundle_proj_3_db_new.c:160-165
             vlg_project_proj(an, bl, xh);
+        } else if constexpr (NA == BA_RAD_NA) {
+            project_radial_new(an, K4, rot_new, j, bl, xh);
         } else {
             double k4[4], Kc[9], R[9];
 #pragma unroll
@@ -2754,6 +2762,7 @@ static inline int grid_for(long long work, int bs, int cap)
     switch (NAEXPR) {                                                               \
     case 6: { constexpr int NA = 6; CALL; } break;                                  \
     case 7: { constexpr int NA = 7; CALL; } break;                                  \
+    case BA_RAD_NA: { constexpr int NA = BA_RAD_NA; CALL; } break;                  \
     case 10: { constexpr int NA = 10; CALL; } break;                                \
     case BA_PROJ_NA: { constexpr int NA = BA_PROJ_NA; CALL; } break;                \
     default: return -1000;                                                          \
@@ -2978,6 +2987,7 @@ int ba_launch_schur_fast(ba_dev *d, double lambda)
     switch (d->na) {
     case 6: return launch_schur_fast<6>(d, lambda);
     case 7: return launch_schur_fast<7>(d, lambda);
+    case BA_RAD_NA: return launch_schur_fast<BA_RAD_NA>(d, lambda);
     case 10: return launch_schur_fast<10>(d, lambda);
     case BA_PROJ_NA: return launch_schur_fast<BA_PROJ_NA>(d, lambda);
     default: return -1000;

@@ -821,7 +821,12 @@ static int ctx_create(const vlgba_problem *p, const vlgba_options *o, vlgba_ctx 
     if (!p || p->m < 1 || p->n < 0 || p->num_obs < 0) return VLGBA_E_ARG;
     if (p->model == VLGBA_MODEL_EUCLIDEAN) {
         if (!p->K) return VLGBA_E_ARG;
-        if (p->num_a != 6 && p->num_a != 7 && p->num_a != 10) return VLGBA_E_NUMA;
+        if (p->num_a != 6 && p->num_a != 7 && p->num_a != 10 && p->num_a != BA_RAD_NA)
+            return VLGBA_E_NUMA;
+        // the radial model lives on the fast path alone: the stage entries do not
+        // cover it, ordered / parity mode (the reference's differences) cannot
+        if (p->num_a == BA_RAD_NA && stage_mode) return VLGBA_E_NUMA;
+        if (p->num_a == BA_RAD_NA && o && o->ordered != 0) return VLGBA_E_ARG;
     } else if (p->model == VLGBA_MODEL_PROJECTIVE) {
         if (p->num_a != BA_PROJ_NA) return VLGBA_E_NUMA;
     } else {
@@ -941,7 +946,8 @@ static int ctx_create(const vlgba_problem *p, const vlgba_options *o, vlgba_ctx 
         c->on_pass = o->on_pass;
         c->on_pass_user = o->on_pass_user;
         c->d.no_mfma = o->schur_kernel == 1;
-        c->d.ndb = o->semantics == 1 ? p->num_a : 6;
+        // (the radial model has no MEX quirk to mimic: all nine rows of da)
+        c->d.ndb = o->semantics == 1 || p->num_a == BA_RAD_NA ? p->num_a : 6;
         c->d.loss_kind = VLGBA_LOSS_NONE;   // vlgba_set_loss
         c->d.loss_scale = 0.0;
         c->d.jac = VLGBA_JAC_FD;            // vlgba_set_jacobian
@@ -951,8 +957,13 @@ static int ctx_create(const vlgba_problem *p, const vlgba_options *o, vlgba_ctx 
             if (!std::strcmp(ev, "analytic") && o->ordered == 0 && !stage_mode)
                 c->d.jac = VLGBA_JAC_ANALYTIC;
         }
+        // the radial model's Jacobian is closed form only (a difference with
+        // h = 1e-10 on k1 is noise), whatever VLGBA_JACOBIAN says
+        if (p->num_a == BA_RAD_NA) c->d.jac = VLGBA_JAC_ANALYTIC;
         rc = ctx_setup(c, p, h, pt_ptr_all, lower_blocks, all_diag, stage_mode);
         if (rc) break;
+        // ... so a problem the planner hands to the ordered kernels is refused
+        if (p->num_a == BA_RAD_NA && c->d.ordered) { rc = VLGBA_E_ARG; break; }
         ST_MARK("setup_end");
         if (c->d.parity) {   // new projections for the sequential new-SSE sum
             rc = ctx_alloc(c, &c->d.xh_out, 2 * (size_t)c->d.N + 2);
@@ -1997,6 +2008,8 @@ int vlgba_set_jacobian(vlgba_ctx *c, int kind)
     if (!c || (kind != VLGBA_JAC_FD && kind != VLGBA_JAC_ANALYTIC)) return VLGBA_E_ARG;
     // ordered / parity mode exists for bit parity with the reference's differences
     if (c->d.ordered) return VLGBA_E_ARG;
+    // the radial model has the closed form only
+    if (c->d.na == BA_RAD_NA && kind != VLGBA_JAC_ANALYTIC) return VLGBA_E_ARG;
     TRY(ctx_enter(c));
     c->d.jac = kind;
     // the table of the current a in the new mode's layout; a camera update the

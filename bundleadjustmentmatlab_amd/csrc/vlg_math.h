@@ -23,6 +23,9 @@
  *                           per-observation loop without changing a bit)
  *   vlg_project_proj        reproject_projective_point of
  *                           toolbox/bundle/mex_bundle_proj_1_XABeUVWeAeB.c:13-32
+ *   vlg_project_radial      the radial-distortion camera (num_a = 9: one focal
+ *                           length, two radial coefficients; not part of the
+ *                           reference)
  *   vlg_drodrigues          dR/dw_k of the exponential map (analytic-Jacobian
  *                           mode; not part of the reference)
  *   vlg_fd_quot             (x1 - x0) / h without a division, bit-identical
@@ -221,6 +224,40 @@ VLG_HD void vlg_project_proj(const double P[12], const double b[3], double x[2])
     double x2 = P[2] * b[0] + P[5] * b[1] + P[8] * b[2] + P[11];
     x[0] = x0 / x2;
     x[1] = x1 / x2;
+}
+
+/* ---- radial-distortion camera (num_a = 9; not part of the reference) --------
+ * a = [w; T; f; k1; k2], the principal point c = (cx, cy) fixed:
+ *   Xc = R b + T,  n = (Xc0, Xc1) / Xc2,  r2 = n'n,
+ *   d = (1 + k1 r2) + (k2 r2) r2,  x = f (d n) + c
+ * (the Bundler / BAL model with a positive focal length and depth).  The one
+ * projection of the model: every kernel that projects calls it, and
+ * vlg_radial_n gives the Jacobian's closed form the same n, r2 and d bit for
+ * bit.  k = a + 6 = [f; k1; k2].                                              */
+VLG_HD void vlg_radial_n(const double k[3], const double R[9], const double t[3],
+                         const double b[3], double n[2], double *iz, double *r2, double *d)
+{
+    double S[3];
+    vlg_rot_b(R, b, S);
+    {
+        const double X0 = S[0] + t[0], X1 = S[1] + t[1], X2 = S[2] + t[2];
+        const double u = X0 / X2, v = X1 / X2;
+        const double q = u * u + v * v;
+        n[0] = u;
+        n[1] = v;
+        *iz = 1.0 / X2;
+        *r2 = q;
+        *d = (1.0 + k[1] * q) + (k[2] * q) * q;
+    }
+}
+
+VLG_HD void vlg_project_radial(const double k[3], const double c[2], const double R[9],
+                               const double t[3], const double b[3], double x[2])
+{
+    double n[2], iz, r2, d;
+    vlg_radial_n(k, R, t, b, n, &iz, &r2, &d);
+    x[0] = k[0] * (d * n[0]) + c[0];
+    x[1] = k[0] * (d * n[1]) + c[1];
 }
 
 /* Finite-difference step of the reference (mex_bundle_1_XABeUVWeAeB.c:23,52). */

@@ -21,7 +21,8 @@ extern "C" {
 #endif
 
 #define VLGBA_E_ARG (-1001)      /* bad size / option                        */
-#define VLGBA_E_NUMA (-1002)     /* num_a not in {6, 7, 10} (Euclidean) / 12 (projective) */
+#define VLGBA_E_NUMA (-1002)     /* num_a not in {6, 7, 9, 10} (Euclidean) / 12 (projective);
+                                    num_a = 9 where the radial model is not covered */
 #define VLGBA_E_ORDER (-1003)    /* observation list not point-major / dups  */
 #define VLGBA_E_NOMEM (-1004)    /* host allocation failed                    */
 #define VLGBA_E_COMM (-1005)     /* RCCL failure                              */
@@ -42,14 +43,17 @@ extern "C" {
  * ones (vlgba_set_jacobian, vlgba_get_jacobian, VLGBA_JAC_*: likewise) and the
  * covariance-method ones (vlgba_set_covariance_method,
  * vlgba_get_covariance_method, vlgba_get_covariance_blocks,
- * vlgba_debug_selinv_plan, VLGBA_COV_*: likewise).  Callers
+ * vlgba_debug_selinv_plan, VLGBA_COV_*: likewise), and the radial-distortion
+ * camera num_a = 9 (a value vlgba_create refused before: no struct, constant or
+ * entry point changed).  Callers
  * check it once at load time with VLGBA_ABI_CHECK() (the MEX gateways and the Python
  * loader do): the library compares the version and the struct sizes the
  * caller was compiled with against its own and returns 0 or VLGBA_E_ABI. */
 #define VLGBA_ABI_VERSION 6
 
 /* camera models (vlgba_problem.model) */
-#define VLGBA_MODEL_EUCLIDEAN 0   /* bundle_euclid.m: a = [w; T; (K)], num_a 6/7/10     */
+#define VLGBA_MODEL_EUCLIDEAN 0   /* bundle_euclid.m: a = [w; T; (K)], num_a 6/7/10;
+                                     num_a = 9: radial distortion (below) */
 #define VLGBA_MODEL_PROJECTIVE 1  /* bundle_projective.m: a = P(:) (3x4), num_a = 12   */
 
 /* ------------------------------------------------------------------------
@@ -60,12 +64,31 @@ extern "C" {
  *                      Xp(1:3,:), bundle_projective.m:76)
  *   obs    visible (point, camera) pairs of x(1:2,:,:) / 'visibility'
  *          (bundle_euclid.m:50,71,102); any order, duplicates rejected.
+ *
+ * Radial distortion (Euclidean model, num_a = 9; beyond the reference): a =
+ * [w(3); T(3); f; k1; k2] per camera -- one focal length and two radial
+ * coefficients, the Bundler / BAL camera with a positive focal length and depth.
+ * The principal point (cx, cy) = K[2], K[3] of the camera is fixed; K[0], K[1]
+ * are unused (as for num_a = 7).  With Xc = R(w) b + T:
+ *     u = Xc0 / Xc2, v = Xc1 / Xc2, r2 = u u + v v, d = 1 + k1 r2 + k2 r2 r2
+ *     x = ( f (d u) + cx , f (d v) + cy )
+ * Its Jacobians are closed form only (a forward difference with h = 1e-10 on k1
+ * is noise): the context is created in VLGBA_JAC_ANALYTIC mode, whatever
+ * VLGBA_JACOBIAN says, and vlgba_set_jacobian(ctx, VLGBA_JAC_FD) returns
+ * VLGBA_E_ARG.  The back substitution uses all nine rows of da, whatever
+ * vlgba_options.semantics says.  It runs on the fast path alone: vlgba_create
+ * returns VLGBA_E_ARG for vlgba_options.ordered != 0 and for a problem that the
+ * planner would hand to the ordered kernels (vlgba_plan_info [15]).  Robust
+ * losses, covariances (both methods), the fix masks, every reduced solve and
+ * sharded contexts work as for the other models.  Not covered (VLGBA_E_NUMA):
+ * vlgba_resect, the vlgba_mex_bundle_* stage entries, the MATLAB drop-ins and
+ * the GPU scene generator.
  * ------------------------------------------------------------------------ */
 typedef struct {
     int m;                 /* cameras                                            */
     int n;                 /* points                                             */
-    int num_a;             /* 6 fix_calibration, 7 fix_principal, 10 variable K;
-                              12 projective                                      */
+    int num_a;             /* 6 fix_calibration, 7 fix_principal, 10 variable K,
+                              9 radial distortion (f, k1, k2); 12 projective    */
     long long num_obs;     /* visible observations                               */
     const int *obs_pt;     /* [num_obs] point index                              */
     const int *obs_cam;    /* [num_obs] camera index                             */
@@ -376,7 +399,9 @@ int vlgba_get_loss(vlgba_ctx *ctx, int *kind, double *scale);
  * the default solver exactly.  The environment variable VLGBA_JACOBIAN=analytic
  * makes analytic the default of every context created with ordered == 0 that
  * stays on the fast path; one the planner hands to the ordered kernels stays
- * VLGBA_JAC_FD (vlgba_get_jacobian tells).  Not covered (forward differences always): ordered /
+ * VLGBA_JAC_FD (vlgba_get_jacobian tells).  The radial-distortion camera
+ * (num_a = 9) has the analytic mode only: VLGBA_JAC_FD is VLGBA_E_ARG there, and
+ * the environment variable has no effect on it.  Not covered (forward differences always): ordered /
  * parity mode, vlgba_resect, the vlgba_mex_bundle_* stage entries and the
  * MATLAB drop-ins. */
 #define VLGBA_JAC_FD 0
