@@ -124,6 +124,11 @@ SIGNATURES = {
     "vlgba_mex_bundle_proj_3": (c_int, [c_int, c_int] + [c_dp] * 12),
     "vlgba_resect": (c_int, [ctypes.POINTER(VlgbaResectProblem), ctypes.POINTER(VlgbaOptions),
                              c_dp, c_dp, c_int, c_ip, ctypes.POINTER(VlgbaStats)]),
+    "vlgba_triangulate": (c_int, [c_int, c_dp, c_dp, c_dp, c_ll, ctypes.POINTER(c_ll), c_ip, c_dp,
+                                  c_int, c_dp, c_ip]),
+    "vlgba_intersect": (c_int, [c_int, c_dp, c_dp, c_dp, c_ll, ctypes.POINTER(c_ll), c_ip, c_dp,
+                                ctypes.POINTER(VlgbaOptions), c_dp, c_dp, c_int, c_ip,
+                                ctypes.POINTER(VlgbaStats)]),
     "vlgba_scene_banded": (c_int, [ctypes.POINTER(VlgbaSceneSpec), c_int,
                                    ctypes.POINTER(VlgbaSceneOut)]),
     "vlgba_version": (c_int, [ctypes.c_char_p, c_int]),

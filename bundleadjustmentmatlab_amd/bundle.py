@@ -31,7 +31,7 @@ from ._lib import (ALLREDUCE_FN, COV_METHODS, JACOBIANS, LOSSES, MODEL_EUCLIDEAN
                    VlgbaStepInfo, c_dp, c_ip, c_up, check, lib)
 
 __all__ = ["bundle_euclid", "bundle_euclid_nomex", "bundle_euclid_obs", "BundleAdjuster",
-           "bundle_euclid_resect",
+           "bundle_euclid_resect", "bundle_euclid_intersect", "triangulate_points",
            "parse_options", "pivot_mask",
            "mex_bundle_1_XABeUVWeAeB", "mex_bundle_2_Se_", "mex_bundle_3_db_new"]
 
@@ -784,6 +784,74 @@ def bundle_euclid_resect(K, Te, w, Xs, xs, *varargin, device=0, max_iter=0, max_
     K_, Te_, w_, _ = unpack(K, a, np.zeros((3, 0)), np.zeros((1, 0)), nvk)
     errs = [err[q, : nerr[q]].copy() for q in range(c)]
     return (K_, Te_, w_, errs, st) if return_stats else (K_, Te_, w_, errs)
+
+
+def _tracks(K, Te, w, obs_ptr, obs_cam, obs_x):
+    """The camera and CSR track arguments of vlgba_triangulate / vlgba_intersect
+    as contiguous buffers (and the ctypes pointers to them)."""
+    K, Te, w = _F(K), _F(Te), _F(w)
+    m = w.shape[1]
+    assert K.shape == (4, m) and Te.shape == (3, m)
+    ptr = np.ascontiguousarray(obs_ptr, dtype=np.int64).reshape(-1)
+    cam = np.ascontiguousarray(obs_cam, dtype=np.int32).reshape(-1)
+    ox = np.ascontiguousarray(obs_x, dtype=np.float64).reshape(-1, 2)
+    assert len(ptr) >= 1 and len(cam) == len(ox) and (len(ptr) == 1 or ptr[-1] == len(cam))
+    keep = (K, Te, w, ptr, cam, ox)
+    args = (m, _dp(K), _dp(Te), _dp(w), len(ptr) - 1,
+            ptr.ctypes.data_as(ctypes.POINTER(ctypes.c_longlong)), cam.ctypes.data_as(c_ip),
+            _dp(ox))
+    return keep, args
+
+
+def triangulate_points(K, Te, w, obs_ptr, obs_cam, obs_x, device=0, return_status=False):
+    """X = triangulation(P, x) (toolbox/geometry/triangulation.m:19-53) for every
+    point of a batch on the GPU (vlgba_triangulate).  K (4 x m), Te, w (3 x m):
+    the pinhole cameras; point i has the views obs_ptr[i] .. obs_ptr[i+1]-1 of
+    obs_cam (camera ids, any order within a point) / obs_x (N x 2 measured
+    image points).  Returns X (4 x n): the point over its 4th entry, or zeros
+    when a view sees it at negative depth (status 0), when it has fewer than two
+    views or the result is not finite (status 2; the reference would return
+    inf / nan for a point at infinity).  ``return_status``: (X, status)."""
+    keep, args = _tracks(K, Te, w, obs_ptr, obs_cam, obs_x)
+    n = args[4]
+    X = np.zeros((4, n), order="F")
+    status = np.zeros(n, dtype=np.int32)
+    check(lib().vlgba_triangulate(*args, int(device), _dp(X), status.ctypes.data_as(c_ip)),
+          "vlgba_triangulate")
+    return (X, status) if return_status else X
+
+
+def bundle_euclid_intersect(K, Te, w, X, obs_ptr, obs_cam, obs_x, device=0, max_iter=0,
+                            max_iter2=0, lambda0=0.0, stop_rel=0.0, return_stats=False):
+    """Batched one-point refinement with the motion fixed --
+
+        [~, ~, ~, X_i] = bundle_euclid(K, T, Omega, X_i, x_i, 'fix_calibration',
+                                       'fix_motion', 'visibility', ones(1, k))
+
+    for every point i at once on the GPU (vlgba_intersect), each point with its
+    own lambda: the mirror image of bundle_euclid_resect.  Cameras and tracks as
+    triangulate_points; X (3 or 4 x n) the start points.  Returns X_ (the same
+    row count; a 4th row is passed through) and the list of per-point error_
+    (SSE / views per accepted step; empty for a point without views, which is
+    left untouched)."""
+    keep, args = _tracks(K, Te, w, obs_ptr, obs_cam, obs_x)
+    n = args[4]
+    X = np.asarray(X, dtype=np.float64)
+    assert X.shape[0] in (3, 4) and X.shape[1] == n
+    b = np.ascontiguousarray(X[:3].T).reshape(-1)      # 3 x n column major
+    cap = (max_iter if max_iter > 0 else 20) + 1
+    err = np.zeros((n, cap))
+    nerr = np.zeros(n, dtype=np.int32)
+    opt = VlgbaOptions()
+    opt.max_iter, opt.max_iter2, opt.lambda0 = int(max_iter), int(max_iter2), float(lambda0)
+    opt.device, opt.stop_rel = int(device), float(stop_rel)
+    st = VlgbaStats()
+    check(lib().vlgba_intersect(*args, ctypes.byref(opt), _dp(b), _dp(err), cap,
+                                nerr.ctypes.data_as(c_ip), ctypes.byref(st)), "vlgba_intersect")
+    X_ = np.array(X, order="F")
+    X_[:3] = b.reshape(n, 3).T
+    errs = [err[q, : nerr[q]].copy() for q in range(n)]
+    return (X_, errs, st) if return_stats else (X_, errs)
 
 
 # ---------------------------------------------------------------------------

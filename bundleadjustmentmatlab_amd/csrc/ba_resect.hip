@@ -23,8 +23,10 @@
 // each: projection + num_a forward-difference columns into LDS), then
 // NA*NA + NA + 1 accumulator lanes walk the tile in order.  The LM control
 // (bundle_euclid.m:205-241, glibc pow for the lambda rule) stays on the host,
-// per problem, exactly as vlgba_run applies it.
+// per problem, exactly as vlgba_run applies it (ba_batch_lm.h, shared with the
+// per-point dual vlgba_intersect of ba_triang.hip).
 #include "ba_camera.h"
+#include "ba_batch_lm.h"
 #include "../../include/vlgba.h"
 
 #include <chrono>
@@ -266,17 +268,9 @@ int dmalloc_n(T **p, size_t n)
     *p = (T *)ba_dmalloc(sizeof(T) * (n ? n : 1));
     return *p ? 0 : -(int)hipErrorOutOfMemory;
 }
-// Per-device pool of a stream and a pinned host block for the per-pass LM
-// scalars: creating a stream and pageable copies cost more than the
-// resection itself (the growing-BA replay calls it once per added camera).
-struct rs_pool {
-    int device;
-    hipStream_t s;
-    double *pin;     // pinned: lam [np] | flags [np] (as doubles) | out [4 np]
-    size_t cap;      // doubles
-};
 std::mutex g_rs_pool_mu;
 std::vector<rs_pool> g_rs_pool;
+}   // namespace
 
 int rs_acquire(int device, size_t need, rs_pool &r)
 {
@@ -312,7 +306,6 @@ void rs_release(const rs_pool &r)
     std::lock_guard<std::mutex> lk(g_rs_pool_mu);
     g_rs_pool.push_back(r);
 }
-}   // namespace
 
 extern "C" int vlgba_resect(const vlgba_resect_problem *pr, const vlgba_options *opt, double *a,
                             double *error_out, int error_cap, int *num_error,
@@ -331,10 +324,6 @@ extern "C" int vlgba_resect(const vlgba_resect_problem *pr, const vlgba_options 
     vlgba_options dflt;
     std::memset(&dflt, 0, sizeof dflt);
     if (!opt) opt = &dflt;
-    const int max_iter = opt->max_iter > 0 ? opt->max_iter : 20;
-    const int max_iter2 = opt->max_iter2 > 0 ? opt->max_iter2 : 10;
-    const double lambda0 = opt->lambda0 > 0 ? opt->lambda0 : 1e-3;
-    const double stop_rel = opt->stop_rel > 0 ? opt->stop_rel : 1e-3;
     VLGBA_CHECK(hipSetDevice(opt->device));
     const auto t0 = std::chrono::steady_clock::now();
     rs_pool pool{opt->device, nullptr, nullptr, 0};
@@ -349,11 +338,7 @@ extern "C" int vlgba_resect(const vlgba_resect_problem *pr, const vlgba_options 
     double *d_X = nullptr, *d_x = nullptr, *d_K = nullptr, *d_a = nullptr, *d_an = nullptr;
     double *d_st = nullptr, *d_lam = nullptr, *d_out = nullptr, *d_fl = nullptr;
     int rc = 0;
-    std::vector<double> lam(np, lambda0), nu(np, 2.0), out(4 * (size_t)np);
-    std::vector<int> fl(np), iter(np, 1), iter2(np, 0), passes(np, 0), acc(np, 0);
-    std::vector<std::vector<double>> err(np);
-    std::vector<int> active(np, 1);
-    int total_passes = 0, total_acc = 0;
+    batch_lm lm((size_t)np, opt);   // the LM control, per problem (ba_batch_lm.h)
     do {
         if ((rc = dmalloc_n(&d_ptr, np + 1)) || (rc = dmalloc_n(&d_X, 3 * (size_t)N)) ||
             (rc = dmalloc_n(&d_x, 2 * (size_t)N)) || (rc = dmalloc_n(&d_K, 4 * (size_t)np)) ||
@@ -375,26 +360,7 @@ extern "C" int vlgba_resect(const vlgba_resect_problem *pr, const vlgba_options 
             rc = -1;
             break;
         }
-        std::vector<int> accepted_prev(np, 0), relin(np, 1);
-        for (;;) {
-            // bundle_euclid.m:120-123 per problem
-            int nact = 0;
-            for (int q = 0; q < np; q++) {
-                if (!active[q]) continue;
-                bool go = iter[q] < max_iter && iter2[q] < max_iter2;
-                if (go && iter[q] >= 3) {
-                    const double e1 = err[q][iter[q] - 1], e0 = err[q][iter[q] - 2];
-                    go = e1 > 1e-20 && e0 - e1 > stop_rel * e0;
-                }
-                if (!go) active[q] = 0;
-                nact += active[q];
-                fl[q] = active[q] | (relin[q] ? 2 : 0) | (accepted_prev[q] ? 4 : 0);
-            }
-            if (!nact) break;
-            for (int q = 0; q < np; q++) {   // pinned staging: one small copy per pass
-                h_lam[q] = lam[q];
-                h_fl[q] = (double)fl[q];
-            }
+        while (lm.stage(h_lam, h_fl)) {
             if (hipMemcpyAsync(d_lam, h_lam, sizeof(double) * 2 * np, hipMemcpyHostToDevice, s) !=
                 hipSuccess) {
                 rc = -1;
@@ -421,39 +387,10 @@ extern "C" int vlgba_resect(const vlgba_resect_problem *pr, const vlgba_options 
                 rc = -1;
                 break;
             }
-            std::memcpy(out.data(), h_out, sizeof(double) * 4 * np);
-            for (int q = 0; q < np; q++) {
-                if (!active[q]) continue;   // a finished problem keeps its last flags
-                accepted_prev[q] = 0;
-                relin[q] = 0;
-                const double old = out[4 * q], nw = out[4 * q + 1], dpg = out[4 * q + 2];
-                const double num_vis = (double)(pr->obs_ptr[q + 1] - pr->obs_ptr[q]);
-                const double rho = (old - nw) / dpg;
-                passes[q]++;
-                total_passes++;
-                if ((old - nw) > 0) {   // bundle_euclid.m:218-232
-                    const double olde = old / num_vis, newe = nw / num_vis;
-                    if ((int)err[q].size() < iter[q]) err[q].push_back(olde);
-                    else err[q][iter[q] - 1] = olde;
-                    iter[q]++;
-                    err[q].push_back(newe);
-                    iter2[q] = 0;
-                    lam[q] = lam[q] * std::max(1.0 / 3.0, 1.0 - std::pow(2.0 * rho - 1.0, 3));
-                    nu[q] = 2.0;
-                    accepted_prev[q] = 1;
-                    relin[q] = 1;
-                    acc[q]++;
-                    total_acc++;
-                } else {                // :233-241
-                    lam[q] = lam[q] * nu[q];
-                    nu[q] = 2.0 * nu[q];
-                    iter2[q]++;
-                }
-            }
+            lm.apply(h_out, pr->obs_ptr);
         }
         if (rc) break;
         // the last accepted step's parameters
-        for (int q = 0; q < np; q++) fl[q] = accepted_prev[q] ? 4 : 0;
         std::vector<double> an((size_t)na * np);
         if (hipMemcpyAsync(a, d_a, sizeof(double) * na * np, hipMemcpyDeviceToHost, s) !=
                 hipSuccess ||
@@ -464,28 +401,15 @@ extern "C" int vlgba_resect(const vlgba_resect_problem *pr, const vlgba_options 
             break;
         }
         for (int q = 0; q < np; q++)
-            if (accepted_prev[q])
+            if (lm.accepted_prev[q])
                 std::memcpy(a + (size_t)na * q, an.data() + (size_t)na * q, sizeof(double) * na);
-        for (int q = 0; q < np; q++) {
-            if (num_error) num_error[q] = (int)err[q].size();
-            if (error_out)
-                for (size_t k = 0; k < err[q].size() && k < (size_t)error_cap; k++)
-                    error_out[(size_t)error_cap * q + k] = err[q][k];
-        }
+        lm.write_errors(error_out, error_cap, num_error);
     } while (0);
     (void)hipStreamSynchronize(s);
     for (void *p : {(void *)d_ptr, (void *)d_X, (void *)d_x, (void *)d_K, (void *)d_a,
                     (void *)d_an, (void *)d_st, (void *)d_lam, (void *)d_out})
         if (p) ba_dfree(p);
     rs_release(pool);
-    if (stats) {
-        stats->iterations = total_passes;
-        stats->accepted = total_acc;
-        stats->num_error = 0;
-        stats->lambda = np ? lam[0] : 0.0;
-        stats->pinv_passes = stats->spin_retries = stats->nd_retries = 0;
-        stats->seconds =
-            std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-    }
+    lm.fill_stats(stats, t0);
     return rc;
 }

@@ -12,7 +12,7 @@ sees the point behind it), removes outliers again and runs ``bundle_euclid``
 a second time.  The BA solves are the hot path and run on the GPU here
 (``bundle_euclid_obs``, and ``bundle_euclid_resect`` for estimate_camera's
 one-camera refinement); the triangulation is triangulation.m's (``_triangulate``,
-numpy); the DLT / RANSAC pose and the outlier removal are out of scope
+numpy, or ``triangulation="gpu"``: ``triangulate_points``); the DLT / RANSAC pose and the outlier removal are out of scope
 (SURVEY.md sec. 2): the new camera starts from the synthetic scene's perturbed
 pose (w0, T0) mapped into the current frame, and no observation is dropped --
 the BA sequence, its growing problem sizes and its visibility subsets are the
@@ -41,7 +41,8 @@ from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
 
-from .bundle import bundle_euclid_obs, bundle_euclid_resect, euclid_obs_adjuster
+from .bundle import (bundle_euclid_obs, bundle_euclid_resect, euclid_obs_adjuster,
+                     triangulate_points)
 from .dist import choose_shards, run_sharded
 from .evaluation import align_scene, vl_irodr, vl_rodr
 
@@ -106,7 +107,7 @@ PREDICT_EARLY_PTS = 3000
 
 def incremental_bundle(sc, fix_calibration=True, init_cams=(0, 1), align=True, device=0,
                        verbose=False, devices=None, shards=None, obs_per_shard=None,
-                       progress=None, prefetch=True):
+                       progress=None, prefetch=True, triangulation="host"):
     """Replay the incremental reconstruction's BA sequence on scene ``sc``
     (scene.Scene).  Cameras ``init_cams`` form the initial two-view
     reconstruction (VLmvg.m's two_view step); every other camera is added in
@@ -119,6 +120,12 @@ def incremental_bundle(sc, fix_calibration=True, init_cams=(0, 1), align=True, d
     rank threads (dist.run_sharded: RCCL across distinct GPUs, host
     collectives between ranks sharing one); without it every solve runs on
     ``device``.
+
+    ``triangulation``: "host" (default) triangulates with numpy on the host
+    (``_triangulate``); "gpu" routes every triangulation -- the replay thread's
+    and the prefetch workers' predictions alike, so that predictions keep
+    matching -- through bundle.triangulate_points (the same rows and camera
+    mask; results differ from the host's by rounding).
 
     ``prefetch`` (fix_calibration, one-rank solves): the next solve's
     observation subset and context are built on a worker thread while the
@@ -135,7 +142,16 @@ def incremental_bundle(sc, fix_calibration=True, init_cams=(0, 1), align=True, d
     resection the added camera's one-camera refinement
     (estimate_camera.m:247-253).  ``progress(solves)``, if given, is called
     after every solve with the solve log so far."""
+    if triangulation not in ("host", "gpu"):
+        raise ValueError(f"triangulation must be 'host' or 'gpu', not {triangulation!r}")
     m, n = sc.m, sc.n
+
+    def triangulate(K_, T_, w_, pts_, status_):
+        if triangulation == "gpu":
+            return _triangulate_gpu(sc, K_, T_, w_, pts_, status_,
+                                    device=devices[0] if devices else device)
+        return _triangulate(sc, K_, T_, w_, pts_, status_)
+
     K = np.array(sc.K, dtype=np.float64)
     T = np.array(sc.T0, dtype=np.float64)
     w = np.array(sc.w0, dtype=np.float64)
@@ -175,7 +191,7 @@ def incremental_bundle(sc, fix_calibration=True, init_cams=(0, 1), align=True, d
         if len(item) >= 6:
             tag, j, cam_on, x3, (Ts, ws, cand), add = item[:6]
             pt_on = x3.copy()
-            pt_on[cand] = _triangulate(sc, K, Ts, ws, cand, cam_on)[3] == 1.0
+            pt_on[cand] = triangulate(K, Ts, ws, cand, cam_on)[3] == 1.0
             if add is not None:
                 cam_on = cam_on.copy()
                 cam_on[add] = True
@@ -405,7 +421,7 @@ def incremental_bundle(sc, fix_calibration=True, init_cams=(0, 1), align=True, d
             resect(j)                                    # :230, estimate_camera.m:247-253
             ba("before-triangulation", j)                # :250-267
             cand = np.nonzero((X[3] == 0) & (nvis_cur >= 2))[0]   # :281-296
-            X[:, cand] = _triangulate(sc, K, T, w, cand, status)
+            X[:, cand] = triangulate(K, T, w, cand, status)
             ba("after-triangulation", j)                 # :300-318
     finally:
         for f in list(pending.values()) + discard:       # a prefetched context not used
@@ -421,6 +437,35 @@ def incremental_bundle(sc, fix_calibration=True, init_cams=(0, 1), align=True, d
                 prefetch=stats)
 
 
+def _tri_rows(sc, pts, status):
+    """Observation ids of points ``pts`` in the cameras of ``status``, grouped
+    by point (each point's views in observation order)."""
+    ids = _obs_of(sc, pts)                               # point-major: rows per point
+    if ids is not None:
+        return ids[np.take(status, np.take(sc.obs_cam, ids))]
+    on = np.zeros(sc.n, dtype=bool)
+    on[pts] = True
+    sel = np.take(on, sc.obs_pt)
+    sel &= np.take(status, sc.obs_cam)
+    sel = np.flatnonzero(sel)
+    # observation order: group the rows by point (stable, so each point's
+    # views keep their order) -- _triangulate's slot / rank arithmetic needs it
+    return sel[np.argsort(sc.obs_pt[sel], kind="stable")]
+
+
+def _triangulate_gpu(sc, K, T, w, pts, status, device=0):
+    """``_triangulate`` on the GPU (bundle.triangulate_points): the same rows
+    (point-major, the cameras of ``status``), one lane per point."""
+    pts = np.asarray(pts)
+    if len(pts) == 0:
+        return np.zeros((4, 0))
+    sel = _tri_rows(sc, pts, status)
+    cnt = np.bincount(np.searchsorted(pts, sc.obs_pt[sel]), minlength=len(pts))
+    ptr = np.concatenate([[0], np.cumsum(cnt)])
+    return triangulate_points(K, T, w, ptr, sc.obs_cam[sel], np.take(sc.obs_x, sel, axis=0),
+                              device=device)
+
+
 def _triangulate(sc, K, T, w, pts, status):
     """triangulation.m for points ``pts`` from their observations in the
     cameras of ``status``: the 2k x 4 system of rows u P3 - P1, v P3 - P2
@@ -430,18 +475,7 @@ def _triangulate(sc, K, T, w, pts, status):
     out = np.zeros((4, len(pts)))
     if len(pts) == 0:
         return out
-    ids = _obs_of(sc, pts)                               # point-major: rows per point
-    if ids is not None:
-        sel = ids[np.take(status, np.take(sc.obs_cam, ids))]
-    else:
-        on = np.zeros(sc.n, dtype=bool)
-        on[pts] = True
-        sel = np.take(on, sc.obs_pt)
-        sel &= np.take(status, sc.obs_cam)
-        sel = np.flatnonzero(sel)
-        # observation order: group the rows by point (stable, so each point's
-        # views keep their order) -- the slot / rank arithmetic below needs it
-        sel = sel[np.argsort(sc.obs_pt[sel], kind="stable")]
+    sel = _tri_rows(sc, pts, status)
     opt, ocam, ox = sc.obs_pt[sel], sc.obs_cam[sel], np.take(sc.obs_x, sel, axis=0)
     R = vl_rodr(w[:, ocam])                              # (k, 3, 3)
     Kc = np.zeros((len(ocam), 3, 3))

@@ -45,7 +45,8 @@ extern "C" {
  * vlgba_get_covariance_method, vlgba_get_covariance_blocks,
  * vlgba_debug_selinv_plan, VLGBA_COV_*: likewise), and the radial-distortion
  * camera num_a = 9 (a value vlgba_create refused before: no struct, constant or
- * entry point changed).  Callers
+ * entry point changed) and the batched per-point entries (vlgba_triangulate,
+ * vlgba_intersect: entry points only).  Callers
  * check it once at load time with VLGBA_ABI_CHECK() (the MEX gateways and the Python
  * loader do): the library compares the version and the struct sizes the
  * caller was compiled with against its own and returns 0 or VLGBA_E_ABI. */
@@ -539,6 +540,52 @@ typedef struct {
  * stop_rel, device are honoured (the rest does not apply). */
 int vlgba_resect(const vlgba_resect_problem *prob, const vlgba_options *opt, double *a,
                  double *error_out, int error_cap, int *num_error, vlgba_stats *stats);
+
+/* ---- batched per-point entries: the dual of vlgba_resect -------------------
+ * m pinhole Euclidean cameras K (4 x m: fx fy cx cy), T (3 x m), w (3 x m) and
+ * n points given by their tracks in CSR form: point i has the views
+ * obs_ptr[i] .. obs_ptr[i+1]-1 (obs_ptr[0] = 0), view o is seen by camera
+ * obs_cam[o] (any order within a point) at obs_x[2 o], obs_x[2 o + 1].
+ * VLGBA_E_ARG, before any device work, for a NULL pointer, m < 1, n < 0, a
+ * non-monotone obs_ptr and a camera id outside [0, m); n == 0 succeeds without
+ * a launch.  Host pointers in and out; thread-safe (a stream per call).
+ * Not covered: the projective and radial models, robust losses, analytic
+ * Jacobians, several GPUs, the MATLAB drop-ins. */
+
+/* X = triangulation(P, x) for every point (replaces toolbox/geometry/
+ * triangulation.m:19-53): P_j = calibration_matrix(K_j) [R(w_j) T_j], the rows
+ * u P_j(3,:) - P_j(1,:), v P_j(3,:) - P_j(2,:) of every view stacked into A, X
+ * the right singular vector of A's smallest singular value over its 4th entry
+ * (here: the eigenvector of A'A by cyclic Jacobi), X = (0, 0, 0, 0) when
+ * P_j(3,:) X < 0 in any view.  One lane per point.  X (4 x n); status (n, may
+ * be NULL): 1 triangulated, 0 rejected by the depth test, 2 fewer than two
+ * views or a non-finite result (X zeros for 0 and 2).  A deliberate deviation:
+ * the reference returns inf / nan when v(4) == 0 (a point at infinity); this
+ * entry returns zeros with status 2. */
+int vlgba_triangulate(int m, const double *K, const double *T, const double *w,
+                      long long n, const long long *obs_ptr, const int *obs_cam,
+                      const double *obs_x, int device, double *X /* 4 x n */,
+                      int *status /* n, may be NULL */);
+
+/* One-point refinement with the motion fixed, every point its own problem with
+ * its own lambda:
+ *   bundle_euclid(K, T, Omega, X_i, x_i, 'fix_calibration', 'fix_motion',
+ *                 'visibility', ones(1, k))
+ * (replaces bundle_euclid.m:111-249 with mex_bundle_1_XABeUVWeAeB.c:43-70,
+ * 196-225, 296-332 and mex_bundle_3_db_new.c:99-166 for n = 1; the LM rule of
+ * bundle_euclid.m:205-241 per point on the host, as vlgba_resect applies it).
+ * Each point's trajectory equals the CPU restatement's (sequential sums, the
+ * closed-form 3 x 3 pseudo-inverse) bit for bit.  X (3 x n) is the start point
+ * and receives the result; error_out (n x error_cap, row i = point i's error_,
+ * SSE / views per accepted step) and num_error (n) may be NULL.  A point with
+ * no views is left untouched, with num_error 0.  opt: max_iter, max_iter2,
+ * lambda0, stop_rel, device are honoured (the rest does not apply). */
+int vlgba_intersect(int m, const double *K, const double *T, const double *w,
+                    long long n, const long long *obs_ptr, const int *obs_cam,
+                    const double *obs_x, const vlgba_options *opt,
+                    double *X /* 3 x n, start point in, result out */,
+                    double *error_out, int error_cap, int *num_error,
+                    vlgba_stats *stats);
 
 /* Multi-GPU: rank 0 creates the 128-byte RCCL unique id, the caller
  * broadcasts it (e.g. torch.distributed) and passes it as opt->comm_id.
