@@ -18,7 +18,12 @@ coefficients 10 % / 20 % off, so every term of the Jacobian is alive.
    with VLGBA_FUSED=0 (k_point_update_chunk's own projection).
 3. One pass: schur_kernel="terms" and solver="dense" against auto at
    tests/test_gpu_nd.py's bars (1e-9 on da, db); the folded camera update on and
-   off, bit-identical.
+   off, bit-identical.  (GPU against GPU.  The Schur complement, every solver
+   and the update at num_a = 9 are held to the references entry by entry in
+   tests/test_gpu_stage_ref.py's radial9-* and *-na9 cases, the chunk kinds of
+   k_schur_mfma in tests/test_gpu_schur_head_na.py, and the long tracks and
+   k_point_cov's LDS edge in tests/test_gpu_track_lengths.py's ladder-9,
+   ladder-9-over and shared-257-na9.)
 4. A whole LM run from k = 0: the reference LM started at the GPU's answer
    lowers the cost by at most 1e-6 relative (the project's restart bar).
 5. Huber at 1e150 is bit-identical to no loss; one Huber pass with planted

@@ -30,6 +30,10 @@ So n = 19, 20, 21 and 41 give short table chunks, and the direct chunks come
 from the longer scenes.  The seeds below were chosen on the CPU for the kinds
 listed.
 
+The cases here are num_a = 6 (three row tiles, the last on 4x4x4 MFMAs).  The
+models, the claims and _solve take num_a (default 6):
+tests/test_gpu_schur_head_na.py runs them at num_a = 7, 9, 10 and 12.
+
 Largest |diff| / bound measured on an MI355X (pytest -s prints every case,
 lines starting SCHUR-HEAD): S 0.033, e_ 0.011 for both kernels (tracks of 2);
 the direct chunks' scenes 0.0021 .. 0.0057 (S), 0.0015 .. 0.0025 (e_).  With
@@ -55,11 +59,29 @@ MF_GROUPS, GROUP_CH = 768, 64   # BA_MF_GROUPS, BA_GROUP_CH
 GS_CAP, GE_CAP = 1536 // 36, 24  # BA_MF_GACC / (6 x 6) blocks, BA_MF_GE_CAP cameras per group
 
 
-def chunk_model(pt, cam, n):
+def cmax_of(na):
+    """BA_MF_CMAX(na): the cameras whose rows fit 16 * BA_MF_RT(na) slab rows."""
+    return 16 * (3 if na == 6 else 4) // na
+
+
+def caps_of(na):
+    """(blocks, cameras) a group's LDS holds (ba_plan.cpp, build_plan's gs_cap
+    and ge_cap of an MFMA group): one chunk's blocks always fit."""
+    c = cmax_of(na)
+    return max(1536 // na ** 2, c * (c + 1) // 2), max(24, c)
+
+
+assert cmax_of(6) == CMAX and caps_of(6) == (GS_CAP, GE_CAP)
+
+
+def chunk_model(pt, cam, n, na=6):
     """The MFMA chunks of build_plan for an observation list sorted
     point-major with cameras ascending, every track of at most CMAX views:
     a list of dicts np, C, words (the record's), direct (20 points, the
-    table is the identity), missing (a 0xff table entry)."""
+    table is the identity), missing (a 0xff table entry).  Of num_a only
+    CMAX depends: the 128 observations, the 20 points and the record's words
+    are the same for every camera model."""
+    CMAX = cmax_of(na)
     ptr = np.searchsorted(pt, np.arange(n + 1))
     cams_of = [tuple(cam[ptr[i]:ptr[i + 1]]) for i in range(n)]
     assert all(0 < len(c) <= CMAX and list(c) == sorted(c) for c in cams_of)
@@ -89,11 +111,12 @@ def chunk_model(pt, cam, n):
     return out
 
 
-def group_model(chunks, G=MF_GROUPS):
+def group_model(chunks, G=MF_GROUPS, na=6):
     """The MFMA groups of build_plan for chunk_model's chunks: chunks spread
     over G groups (VLGBA_SCHUR_GROUPS, else BA_MF_GROUPS), a group closed
-    early where its blocks or cameras would pass the LDS caps.  A list of
-    (first chunk, one past the last, blocks, cameras) per group."""
+    early where its blocks or cameras would pass the LDS caps of num_a.  A
+    list of (first chunk, one past the last, blocks, cameras) per group."""
+    GS_CAP, GE_CAP = caps_of(na)
     n, out, c, k = len(chunks), [], 0, 0
     while c < n:
         tend = ((k + 1) * n + G - 1) // G
@@ -176,8 +199,8 @@ CASES = {
 }
 
 
-def _claims(key, chunks):
-    c = CASES[key]
+def _claims(key, chunks, na=6, cases=None):
+    c = (cases or CASES)[key]
     kinds = dict(direct=any(k["direct"] for k in chunks),
                  table=any(not k["direct"] for k in chunks),
                  missing=any(k["missing"] for k in chunks),
@@ -203,10 +226,11 @@ def _env_groups():
     return int(e) if e.isdigit() and int(e) > 0 else MF_GROUPS
 
 
-def _check_plan(key, plan, chunks, groups):
+def _check_plan(key, plan, chunks, groups, na=6):
     """The models are the planner's chunking and grouping: same chunks, blocks,
     camera slots and record words, same groups with the same blocks and
     cameras; every chunk on the MFMA kernel."""
+    assert plan["num_a"] == na, (key, plan)
     assert plan["mfma"] == 1 and plan["reordered"] == 0 and plan["long_points"] == 0, (key, plan)
     assert plan["chunks"] == len(chunks), (key, plan["chunks"], len(chunks))
     assert plan["chunk_slots"] == sum(len(k["pairs"]) for k in chunks), key
@@ -217,19 +241,36 @@ def _check_plan(key, plan, chunks, groups):
     assert plan["group_eslots"] == sum(g[3] for g in groups), (key, plan, groups)
 
 
-def _solve(pkg, key):
+def _start(sc, na, pt, cam, ox):
+    """(K, a, b, observations, constructor keywords) of a scene at num_a: the
+    parameters of tests/test_gpu_stage_ref.py (6, 7, 10), the projective
+    cameras of scene.projective_from (12), and for the radial camera (9)
+    tests/test_gpu_radial.py's start and observations through the lens."""
+    b = np.asfortranarray(sc.X0[:3])
+    if na == 12:
+        from bundleadjustmentmatlab_amd.scene import projective_from
+        Pp, Xp = projective_from(sc)
+        return (None, np.asfortranarray(Pp.reshape(12, sc.m, order="F")),
+                np.asfortranarray(Xp[0:3]), ox, dict(model="projective", m=sc.m))
+    if na == 9:
+        from test_gpu_stage_ref import _radial
+        a, b, ox = _radial(sc, pt, cam)
+        return sc.K, a, b, ox, {}
+    from test_gpu_stage_ref import _params
+    return sc.K, _params(sc, na)[0], b, ox, {}
+
+
+def _solve(pkg, key, na=6, cases=None):
     """One case on the GPU: (kinds, plan, ratios of the MFMA kernel, ratios of
     the per-term kernel); asserts the bit-for-bit repeat."""
-    c = CASES[key]
+    c = (cases or CASES)[key]
     sc, pt, cam, ox = _scene(*c["args"], drop=c.get("drop"))
-    chunks = chunk_model(pt, cam, sc.n)
-    kinds = _claims(key, chunks)
-    a = np.zeros((6, sc.m), order="F")
-    a[0:3], a[3:6] = sc.w0, sc.T0
-    b = np.asfortranarray(sc.X0[:3])
+    chunks = chunk_model(pt, cam, sc.n, na)
+    kinds = _claims(key, chunks, na, cases)
+    K, a, b, ox, kw = _start(sc, na, pt, cam, ox)
     out = {}
     for kern in ("auto", "terms"):
-        with pkg.BundleAdjuster(sc.K, pt, cam, ox, sc.n, 6, schur_kernel=kern) as ba:
+        with pkg.BundleAdjuster(K, pt, cam, ox, sc.n, na, schur_kernel=kern, **kw) as ba:
             ba.set_params(a, b)
             lin = ba.linearization()
             jk, blocks, e_ = (x.copy() for x in ba.reduced_system(dense=False))
@@ -238,11 +279,11 @@ def _solve(pkg, key):
         assert np.array_equal(jk, jk2) and np.array_equal(blocks, blocks2), (key, kern)
         assert np.array_equal(e_, e2), (key, kern)
         if kern == "auto":
-            _check_plan(key, plan, chunks, group_model(chunks, _env_groups()))
+            _check_plan(key, plan, chunks, group_model(chunks, _env_groups(), na), na)
             out["plan"] = plan
         else:
             assert plan["mfma"] == 0 and plan["mfma_groups"] == 0, (key, plan)
-        ref = sr.schur(sc.m, sc.n, 6, pt, cam, lin["W"], lin["V"], lin["eB"], lin["U"],
+        ref = sr.schur(sc.m, sc.n, na, pt, cam, lin["W"], lin["V"], lin["eB"], lin["U"],
                        lin["eA"], 1e-3)
         got = set(map(tuple, jk.tolist()))
         nz = np.flatnonzero(np.any(ref["S"] != 0, axis=(1, 2)))
@@ -300,17 +341,17 @@ ONE_GROUP = {
 }
 
 
-def _group_claims(key, G):
+def _group_claims(key, G, na=6, cases=None, one_group=None):
     """The model's groups of a case with G groups asked for, and their kinds;
     fails where the groups do not show what ONE_GROUP lists (G = 1)."""
-    c = CASES[key]
+    c = (cases or CASES)[key]
     sc, pt, cam, ox = _scene(*c["args"], drop=c.get("drop"))
-    chunks = chunk_model(pt, cam, sc.n)
-    groups = group_model(chunks, G)
+    chunks = chunk_model(pt, cam, sc.n, na)
+    groups = group_model(chunks, G, na)
     kinds = group_kinds(chunks, groups)
     if G == 1:
         assert kinds["several"], (key, groups)
-        for name, want in ONE_GROUP[key].items():
+        for name, want in (one_group or ONE_GROUP)[key].items():
             assert (want <= kinds["C"]) if name == "C" else kinds[name], (key, name, kinds, groups)
         if c.get("drop") is not None:   # the chunk with the removed view has neighbours
             assert groups[0][1] - groups[0][0] >= 2, (key, groups)

@@ -21,6 +21,10 @@ C. update  k_update_linearize's db within the bound of the long double back
 Shapes: n = 1327 (prime: partial MFMA K-blocks and a partial last chunk);
 m = 33 / 33 / 34 / 33 cameras for num_a = 6 / 7 / 10 / 12 (camera-aligned CR
 tiles of 5 / 4 / 3 / 2 cameras: the last tile is partial), and m = 32 for 6.
+The radial camera (num_a = 9: parameters and observations through the lens as
+tests/test_gpu_radial.py, all nine rows of da in the back substitution) has
+27-row CR tiles of three cameras: m = 34 / 33 / 35 leave one / three / two
+cameras in the last tile.
 
 The solve stage runs all five solvers on every banded shape (auto in the
 stage cases; per-level CR, envelope, dense, sequential beside them), nd and
@@ -31,7 +35,8 @@ Every test prints its figures before it asserts (lines starting STAGE-REF,
 pytest -s).  Measured on an MI355X; no bar was widened.
 
 Largest |diff| / bound per stage:
-    S     banded 0.0008 .. 0.0011 (MFMA and terms, num_a 6 / 7 / 10 / 12);
+    S     banded 0.0008 .. 0.0012 (MFMA and terms, num_a 6 / 7 / 9 / 10 / 12;
+          num_a 9: 0.0011 .. 0.0012, e_ 0.0004 .. 0.0008, db 0.019 .. 0.020);
           lambda 10: 0.014; mixed plan 0.18; tracks of 10: 0.0008;
           long tracks 0.30 (k_schur_long_acc and k_schur_reduce's pairs:
           the same), one point in 140 cameras 0.091; two cameras, one
@@ -45,9 +50,13 @@ eta / (ld u) of the solve, GPU | LAPACK Cholesky on the same S:
     num_a  6, m 33 (198)   0.019 | 0.0096  0.019 | 0.0096  0.052 | 0.0096  0.052 | 0.0096  0.016 | 0.0096
     num_a  6, m 32 (192)   0.026 | 0.0090  0.026 | 0.0090  0.042 | 0.0090  0.042 | 0.0090  0.020 | 0.0090
     num_a  7, m 33 (231)   0.015 | 0.0071  0.015 | 0.0071  0.023 | 0.0071  0.023 | 0.0071  0.014 | 0.0071
+    num_a  9, m 34 (306)   0.0065 | 0.0047 0.0065 | 0.0047 0.0083 | 0.0047 0.0083 | 0.0047 0.011 | 0.0047
     num_a 10, m 34 (340)   0.0091 | 0.0050 0.0091 | 0.0050 0.013 | 0.0050  0.013 | 0.0050  0.011 | 0.0050
     num_a 12, m 33 (396)   0.0082 | 0.0038 0.0082 | 0.0038 0.012 | 0.0038  0.012 | 0.0038  0.0055 | 0.0038
     ladybug, m 120 (720)   nd 0.0080 | 0.0047              0.0088 | 0.0047
+    the same, num_a 9 (1080) nd 0.0080 | 0.0036            0.0082 | 0.0036
+    num_a 9, one-launch CR: m 33 (297) 0.011 | 0.0063, m 35 (315) 0.0078 | 0.0054,
+    terms 0.0095 | 0.0055, pivot 0.015 | 0.0078
     other auto cases: lambda 10 0.020 | 0.015, terms 0.015 | 0.014, mixed
     0.012 | 0.0094, tracks of 10 0.030 | 0.010, long tracks 0.0036 | 0.0035,
     140-camera point 0.012 | 0.0038, unseen camera 0.030 | 0.033, single-view
@@ -64,7 +73,7 @@ import schur_ref as sr
 
 pytestmark = pytest.mark.gpu
 
-TRACK = {6: 6, 7: 5, 10: 4, 12: 3}        # G + 1 cameras: S tridiagonal in G-camera tiles
+TRACK = {6: 6, 7: 5, 9: 4, 10: 4, 12: 3}   # G + 1 cameras: S tridiagonal in G-camera tiles
 ROWS = {na: na * (32 // na) for na in TRACK}   # the whole cameras that fit a 32-row CR tile
 
 
@@ -76,6 +85,18 @@ def _params(sc, na):
     elif na == 10:
         a[6:10] = sc.K
     return a, np.asfortranarray(sc.X0[:3])
+
+
+def _radial(sc, pt, cam):
+    """The radial camera (num_a = 9) on a scene, as tests/test_gpu_radial.py::_rscene:
+    (a (9, m), b, observations): the scene's perturbed poses and points with
+    coefficients 10 % / 20 % off the truth, and the true scene's observations
+    through the lens (k1 = -0.15, k2 = 0.03) plus 0.5 px noise."""
+    import radial_ref as ra
+    kt = np.tile(np.array(ra.K_TRUE)[:, None], (1, sc.m))
+    ox = ra.observe(sc.K, ra.pack(sc.K, sc.w, sc.T, kt), sc.X, pt, cam, 0.5, 77)
+    a = ra.pack(sc.K, sc.w0, sc.T0, kt * np.array([[0.9], [1.2]]))
+    return a, np.asfortranarray(sc.X0[:3]), ox
 
 
 def _obs(sc):
@@ -206,13 +227,23 @@ STAGE = {
     "fix-motion": _case(lambda: _banded(6, 33), fixed="all", fix_motion=True),
     "fix-structure": _case(lambda: _banded(6, 33), fix_structure=True),
     "nomex10": _case(lambda: _banded(10, 34), na=10, plan=_mfma_cr(10), semantics="nomex"),
+    # the radial camera: 27-row CR tiles of three cameras; the last tile holds
+    # one camera (m = 34), three (m = 33), two (m = 35)
+    "radial9-m34": _case(lambda: _banded(9, 34), na=9, plan=_mfma_cr(9), launches=FUSED),
+    "radial9-m34-terms": _case(lambda: _banded(9, 34), na=9, plan=_terms_cr(9),
+                               schur_kernel="terms"),
+    "radial9-m33": _case(lambda: _banded(9, 33), na=9, plan=_mfma_cr(9), launches=FUSED),
+    "radial9-m35": _case(lambda: _banded(9, 35), na=9, plan=_mfma_cr(9), launches=FUSED),
+    "radial9-pivot": _case(lambda: _banded(9, 34), na=9, plan=_mfma_cr(9), fixed=(0, 1),
+                           pivot="first2"),
 }
 # the solve stage alone: the other four solvers on every banded shape, and
 # the nested-dissection order (tests/test_gpu_nd.py's scene)
 _NOCR = lambda p: p["cr_levels"] == 0 and p["nd_arcs"] == 0    # noqa: E731
 SOLVE = {}
 for _name, _na, _m in (("banded6-m33", 6, 33), ("banded6-m32", 6, 32), ("banded7-m33", 7, 33),
-                       ("banded10-m34", 10, 34), ("projective12-m33", 12, 33)):
+                       ("banded10-m34", 10, 34), ("projective12-m33", 12, 33),
+                       ("radial9-m34", 9, 34)):
     _kw = dict(model="projective") if _na == 12 else {}
     _sc = (lambda na, m: lambda: _banded(na, m))(_na, _m)
     SOLVE[_name + "-levels"] = _case(_sc, na=_na, plan=_cr(_na), launches=LEVELS,
@@ -224,11 +255,16 @@ SOLVE["ladybug120-nd"] = _case(lambda: _ladybug(m=120, n=12000, seed=3), solver=
                                plan=lambda p: p["nd_arcs"] >= 2 and p["cr_levels"] == 0)
 SOLVE["ladybug120-envelope"] = _case(lambda: _ladybug(m=120, n=12000, seed=3), plan=_NOCR,
                                      solver="envelope")
+SOLVE["ladybug120-nd-na9"] = _case(lambda: _ladybug(m=120, n=12000, seed=3), na=9, solver="nd",
+                                   plan=lambda p: p["nd_arcs"] >= 2 and p["cr_levels"] == 0)
+SOLVE["ladybug120-envelope-na9"] = _case(lambda: _ladybug(m=120, n=12000, seed=3), na=9,
+                                         plan=_NOCR, solver="envelope")
 CASES = dict(STAGE, **SOLVE)
 # the update stage's list: banded 6 / 10, mixed, long tracks, nomex, unseen
 # points and fix_structure (db == 0 exactly), the masks
 UPDATE = ["banded6-m33", "banded6-m33-lam10", "banded10-m34", "mixed", "long-acc", "long-140",
-          "nomex10", "points-unseen-single", "fix-structure", "pivot", "tracks10"]
+          "nomex10", "points-unseen-single", "fix-structure", "pivot", "tracks10",
+          "radial9-m34", "radial9-pivot"]
 
 
 @contextlib.contextmanager
@@ -275,6 +311,8 @@ def _run_case(gpu, key, cases=None):
         Pp, Xp = projective_from(sc)
         a, b = np.asfortranarray(Pp.reshape(12, m, order="F")), np.asfortranarray(Xp[0:3])
         K, kw["m"] = None, m
+    elif na == 9:
+        (a, b, ox), K = _radial(sc, pt, cam), sc.K
     else:
         (a, b), K = _params(sc, na), sc.K
     if isinstance(kw.get("pivot"), str):
@@ -360,7 +398,9 @@ def test_update_stage(gpu, key):
     r = _run(gpu, key)
     _facts(r, key)
     na, L = r["na"], r["lin"]
-    ndb = na if r["kw"].get("semantics") == "nomex" else 6
+    # (the radial camera's back substitution takes all nine rows of da under
+    # either semantics: ba_solver.cpp, ndb of the radial model)
+    ndb = na if r["kw"].get("semantics") == "nomex" or na == 9 else 6
     Vinv = sr.vinv_of(L["V"], r["lam"])
     ref, bound = sr.back_subst(na, ndb, r["pt"], r["cam"], L["W"], Vinv, L["eB"], r["da"])
     ratio = sr.db_ratio(r["db"], ref, bound)

@@ -8,13 +8,15 @@ Ladders (m = 280, two tracks of every length on a threshold: BA_MF_CMAX(na) | +1
 8 | 9, 32 | 33, 90 | 91, 128 | 129, 256 | 257, and the longest): three full
 segments per track, the second trip of k_long_db's loop, k_long_y / k_long_db /
 k_schur_long_acc / k_schur_reduce's pair loop / the segment chunks of the
-linearisation for num_a 6, 7, 10 and 12, ndb = num_a (nomex).
+linearisation for num_a 6, 7, 9, 10 and 12, ndb = num_a (nomex; the radial
+camera always).
     ladder-6 (top 257), ladder-7 (257), ladder-10 (273), ladder-10-over (274),
-    ladder-10-nomex (273), ladder-12 (projective, 280)
+    ladder-10-nomex (273), ladder-12 (projective, 280), ladder-9 (radial, 304
+    cameras, top 303), ladder-9-over (radial, 304 cameras, top 304)
 Shared (m = 100, C tracks of 91..100 views through cameras 0..89): per-camera
 long lists and per-block pair counts of C = 48 | 49 (BA_LMATCH_BATCH), 64 | 65
 (k_long_pairs' second round), 256 | 257 (BA_LCAM_LDS: the sequential merge),
-num_a 6; C = 257 also at num_a 10 and 12.
+num_a 6; C = 257 also at num_a 9, 10 and 12.
 Every case runs with VLGBA_LONG_ACC=1 and =0; the two routes' reduced system
 and step are bit-identical.  Plan facts of every case: ordered == 0,
 reordered == 1, 0 < mfma_groups < groups, long_points == the planted tracks of
@@ -22,11 +24,15 @@ at least 91 views.
 
 A. Schur / solve / update: the three checks of test_gpu_stage_ref.py.
 B. linearisation of the ladders: W bit-identical to the oracle's, V / eB and
-   U / eA at test_long_tracks_fast_path's 1e-13 bars.
+   U / eA at test_long_tracks_fast_path's 1e-13 bars.  The oracle has no
+   radial camera: the num_a = 9 ladders' residuals and U, eA, V, eB, W are held
+   to the propagated bounds of tests/radial_ref.py instead (|diff| / bound <= 1,
+   as tests/test_gpu_radial.py does on its scenes).
 C. k_point_cov on the ladders (first two cameras pivot) as
    test_gpu_covariance.py::test_point_stage: all three bins; the workgroup
    launch stages its W rows in LDS up to 273 views at num_a 10 (65520 B) and
-   reads global memory at 274 (65760 B > BA_COV_LDS).
+   reads global memory at 274 (65760 B > BA_COV_LDS); at num_a 9 the edge is
+   303 | 304 views (65448 B | 65664 B).
 
 A long double reference is computed once per scene and shared by the two
 routes after their inputs were compared bit for bit (they are the same
@@ -48,6 +54,8 @@ Largest |diff| / bound per stage:
     ladder-10-over     0.28     0.044    0.047 (0.028)
     ladder-10-nomex    0.28     0.046    0.040 (0.014)
     ladder-12          0.23     0.059    0.056 (0.036)
+    ladder-9           0.24     0.018    0.028 (0.014)
+    ladder-9-over      0.27     0.023    0.040 (0.016)
     shared-48          0.076    0.0028   0.067 (0.0016)
     shared-49          0.056    0.011    0.051 (0.0021)
     shared-64          0.051    0.0033   0.038 (0.0018)
@@ -56,17 +64,22 @@ Largest |diff| / bound per stage:
     shared-257         0.027    0.0026   0.046 (0.0029)
     shared-257-na10    0.027    0.0033   0.044 (0.0015)
     shared-257-na12    0.030    0.0029   0.044 (0.0023)
+    shared-257-na9     0.029    0.0030   0.033 (0.00092)
 eta / (ld u) of the solve, GPU | LAPACK Cholesky on the same S:
     ladder-6 (ld 1680) 0.0019 | 0.0020, ladder-7 (1960) 0.0017 | 0.0021,
     ladder-10 and -nomex (2800) 0.0013 | 0.0013, ladder-10-over 0.0013 | 0.0013,
     ladder-12 (3360) 0.0010 | 0.0011, shared-49 (600) 0.0046 | 0.0074,
-    shared-257 0.0047 | 0.0058.
+    shared-257 0.0047 | 0.0058, ladder-9 (2736) 0.0015 | 0.0018, ladder-9-over
+    0.0014 | 0.0016, shared-257-na9 (900) 0.0038 | 0.0037.
 Linearisation: W bit-identical in all five ladders; max |diff| / max |ref| of
     V 4.5e-16 .. 9.5e-16, eB 2.4e-16 .. 1.3e-15, U 2.6e-16 .. 4.3e-16,
-    eA 1.6e-16 .. 5.1e-16 (the bars are 1e-13).
+    eA 1.6e-16 .. 5.1e-16 (the bars are 1e-13).  The radial ladders, largest
+    |diff| / bound: ladder-9 U 0.098 eA 0.083 V 0.051 eB 0.046 W 0.15, residuals
+    0.17; ladder-9-over U 0.097 eA 0.085 V 0.051 eB 0.046 W 0.15, residuals 0.19.
 Point covariances, largest |diff| / bound: ladder-6 0.057, ladder-7 0.051,
     ladder-10 0.0041 (65520 B of W rows, in LDS), ladder-10-over 0.0032
-    (65760 B, from global memory); planted lengths up to 8 took the 8-lane
+    (65760 B, from global memory), ladder-9 0.033 (65448 B, in LDS),
+    ladder-9-over 0.033 (65664 B, from global memory); planted lengths up to 8 took the 8-lane
     launch, 9 .. 32 one wave, 33 and more one workgroup.
 """
 import numpy as np
@@ -89,19 +102,24 @@ LADDER = {
     "ladder-10-over": (10, 274, {}),
     "ladder-10-nomex": (10, 273, dict(semantics="nomex")),
     "ladder-12": (12, 280, dict(model="projective")),
+    # the radial camera on 304 cameras: k_point_cov's LDS edge at num_a = 9 is 303 | 304 views
+    "ladder-9": (9, 303, {}),
+    "ladder-9-over": (9, 304, {}),
 }
+LADDER_M = {"ladder-9": 304, "ladder-9-over": 304}      # cameras, where not ladder()'s 280
 # name: (num_a, C, constructor keywords)
 SHARED = {f"shared-{C}": (6, C, {}) for C in (48, 49, 64, 65, 256, 257)}
 SHARED["shared-257-na10"] = (10, 257, {})
 SHARED["shared-257-na12"] = (12, 257, dict(model="projective"))
-SHARED_SOLVE = ["shared-49", "shared-257"]       # the solve does not depend on C
+SHARED["shared-257-na9"] = (9, 257, {})
+SHARED_SOLVE = ["shared-49", "shared-257", "shared-257-na9"]   # the solve does not depend on C
 # restated from ba_internal.h
 COV_T8, COV_T64, COV_LDS = 8, 32, 65536
 
 
 def _scene(name):
     if name in LADDER:
-        return ts.ladder(LADDER[name][0], LADDER[name][1])
+        return ts.ladder(LADDER[name][0], LADDER[name][1], m=LADDER_M.get(name, 280))
     return ts.shared(SHARED[name][1])
 
 
@@ -209,7 +227,7 @@ def test_solve_stage(gpu, oracle, key):
 def test_update_stage(gpu, key):
     r = _run(gpu, key)
     na, L = r["na"], r["lin"]
-    ndb = na if r["kw"].get("semantics") == "nomex" else 6
+    ndb = na if r["kw"].get("semantics") == "nomex" or na == 9 else 6   # radial: all nine rows
     Vinv = _memo(("vinv", key.split("/")[0]), [L["V"]], lambda: sr.vinv_of(L["V"], r["lam"]))
     ref, bound = sr.back_subst(na, ndb, r["pt"], r["cam"], L["W"], Vinv, L["eB"], r["da"])
     ratio = sr.db_ratio(r["db"], ref, bound)
@@ -271,14 +289,49 @@ def test_linearisation(gpu, oracle, poracle, name):
         assert np.max(np.abs(lin[nm] - ref[nm])) <= 1e-13 * np.max(np.abs(ref[nm])), nm
 
 
+@pytest.mark.parametrize("name", ["ladder-9", "ladder-9-over"])
+def test_linearisation_radial(gpu, name):
+    """The oracle has no radial camera: the ladder's residuals and its
+    linearisation (the segment chunks of the 129-, 257-, 303- and 304-view
+    tracks at num_a = 9) within the propagated bounds of tests/radial_ref.py, as
+    tests/test_gpu_radial.py::test_linearisation_within_the_reference_bounds."""
+    import radial_ref as ra
+    import robust_ref as rr
+    r = _run(gpu, f"{name}/acc1")
+    sc, pt, cam, _ = _scene(name)
+    a, b, ox = stage._radial(sc, pt, cam)
+    assert np.array_equal(a, r["a"]) and np.array_equal(b, r["b"])
+    with gpu.BundleAdjuster(sc.K, pt, cam, ox, sc.n, 9, lambda0=r["lam"]) as ba:
+        ba.set_params(a, b)
+        lin = ba.linearization()
+        e = ba.residuals()[0]
+    for k in ("U", "eA", "V", "eB", "W"):      # the case's own linearisation is this one
+        assert np.array_equal(lin[k], r["lin"][k]), (name, k)
+    eref, eb = ra.residuals(sc.K, a, b, pt, cam, ox)
+    R = ra.linearization(sc.K, a, b, pt, cam, e, sc.m, sc.n)
+    fig = {k: rr.ratio(lin[k], R[k], R[k + "_b"]) for k in ("U", "eA", "V", "eB", "W")}
+    fig["e"] = rr.ratio(e, eref, eb)
+    first = int(np.searchsorted(pt, sc.base_n))
+    planted = rr.ratio(lin["W"][:, :, first:], R["W"][:, :, first:], R["W_b"][:, :, first:])
+    print(f"TRACK-REF linearise {name}: largest |diff| / bound "
+          + " ".join(f"{k} {v:.3g}" for k, v in fig.items())
+          + f" (W of the planted tracks {planted:.3g}; longest track {np.bincount(pt).max()})")
+    assert np.all(np.abs(lin["W"][6:9]).max(axis=(1, 2)) > 0)       # f, k1, k2 rows alive
+    assert all(v <= 1.0 for v in fig.values()), (name, fig)
+
+
 # ---------------------------------------------------------------------------
 # C. the covariance's point stage
 # ---------------------------------------------------------------------------
-@pytest.mark.parametrize("name", ["ladder-6", "ladder-7", "ladder-10", "ladder-10-over"])
+@pytest.mark.parametrize("name", ["ladder-6", "ladder-7", "ladder-10", "ladder-10-over",
+                                  "ladder-9", "ladder-9-over"])
 def test_point_cov(gpu, name):
     na = LADDER[name][0]
     sc, pt, cam, ox = _scene(name)
-    a, b = _params(sc, na)
+    if na == 9:
+        a, b, ox = stage._radial(sc, pt, cam)
+    else:
+        a, b = _params(sc, na)
     with gpu.BundleAdjuster(sc.K, pt, cam, ox, sc.n, na, pivot=np.arange(sc.m) < 2) as ba:
         ba.set_params(a, b)
         L = ba.linearization()
@@ -302,9 +355,11 @@ def test_point_cov(gpu, name):
           f"{'staged in LDS' if staged else 'read from global memory'}")
     assert all(bins.values()) and 8 in bins["8 lanes"] and 9 in bins["one wave"]
     assert 32 in bins["one wave"] and 33 in bins["one workgroup"]
-    assert staged == (name != "ladder-10-over")
+    assert staged == (not name.endswith("-over"))
     if na == 10:
         assert need == (65520 if staged else 65760)
+    if na == 9:
+        assert need == (65448 if staged else 65664)
     pts = cov["pts"]
     assert np.array_equal(pts, pts.transpose(1, 0, 2)), name
     assert np.all(track > 0) and np.all(np.isfinite(pts))

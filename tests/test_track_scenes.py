@@ -7,7 +7,15 @@ import pytest
 
 import track_scenes as ts
 
-LADDERS = [(6, 257), (7, 257), (10, 273), (10, 274), (12, 280)]
+LADDERS = [(6, 257), (7, 257), (10, 273), (10, 274), (12, 280), (9, 303, 304), (9, 304, 304)]
+# sha256 (first 16 digits) over pt, cam, ox, X, X0 of the m = 280 ladders, the
+# observation count, the last observation's x and the last landmark's start z,
+# recorded before ladder() took its m keyword
+RECORDED = {(6, 257): ("ab04f4c67d9294f1", 4056, 266.09222295817017, -12.865866604488387),
+            (7, 257): ("bb92af63ffa05c4e", 4098, 248.63849822473307, 0.03135371800370057),
+            (10, 273): ("5646f97cc7294941", 4640, 273.8215188273276, 0.9300141163828215),
+            (10, 274): ("a64439c9701a30e1", 4642, 273.23803925364547, 0.9282356540785651),
+            (12, 280): ("faa00f00ca531d59", 4594, 243.41584476042246, 8.034343501975139)}
 SHARED = [48, 49, 64, 65, 256, 257]
 
 
@@ -30,11 +38,27 @@ def _well_formed(sc, pt, cam, ox):
     assert 0 < r[pt >= sc.base_n].min() and r.max() < 4.0
 
 
-@pytest.mark.parametrize("na,top", LADDERS)
-def test_ladder(na, top):
-    sc, pt, cam, ox = ts.ladder(na, top)
+@pytest.mark.parametrize("key", list(RECORDED))
+def test_ladders_of_280_cameras_are_unchanged(key):
+    """The m keyword left the existing scenes bit for bit what they were."""
+    import hashlib
+    sc, pt, cam, ox = ts.ladder(*key)
+    assert all(np.array_equal(x, y) for x, y in zip(ts.ladder(*key, m=280)[1:], (pt, cam, ox)))
+    h = hashlib.sha256()
+    for x in (pt, cam, ox, sc.X, sc.X0):
+        h.update(np.ascontiguousarray(x).tobytes())
+    digest, nobs, last_x, last_z = RECORDED[key]
+    assert (len(pt), float(ox[-1, 0]), float(sc.X0[2, -1])) == (nobs, last_x, last_z)
+    assert h.hexdigest()[:16] == digest
+
+
+@pytest.mark.parametrize("args", LADDERS, ids=["-".join(map(str, a)) for a in LADDERS])
+def test_ladder(args):
+    na, top = args[:2]
+    m = args[2] if len(args) > 2 else 280
+    sc, pt, cam, ox = ts.ladder(*args)
     _well_formed(sc, pt, cam, ox)
-    assert (sc.m, sc.base_n) == (280, 400)
+    assert (sc.m, sc.base_n) == (m, 400)
     base, lad = ts.track_lengths(sc, pt)
     assert base.max() <= 30 and base.min() >= 1        # long_points is the planted ones'
     want = ts.ladder_lengths(na, top)

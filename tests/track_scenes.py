@@ -9,7 +9,8 @@ centre is in front of every camera, so ANY camera list is a valid track: a
 track's length, and which cameras share it, are chosen and not drawn.
 
     planted(m, base_n, tracks, seed)  one landmark per camera list
-    ladder(na, top)   two landmarks (a window of consecutive cameras, a random
+    ladder(na, top, m=280)
+                      two landmarks (a window of consecutive cameras, a random
                       camera set) of every length on a threshold of the fast
                       path: BA_MF_CMAX(na) and + 1 (MFMA | per-term chunk), 8 |
                       9 and 32 | 33 (k_point_cov's bins), 90 | 91 (per-term |
@@ -24,7 +25,7 @@ import functools
 import numpy as np
 
 RADIUS = 150.0
-CMAX = {6: 8, 7: 9, 10: 6, 12: 5}      # BA_MF_CMAX(na), ba_internal.h
+CMAX = {6: 8, 7: 9, 9: 7, 10: 6, 12: 5}   # BA_MF_CMAX(na), ba_limits.h
 CH_OBS, CH_TERMS = 128, 4096           # BA_CH_OBS, BA_CH_TERMS
 
 
@@ -73,12 +74,12 @@ def ladder_lengths(na, top):
 
 
 @functools.lru_cache(maxsize=None)
-def ladder(na, top):
-    """m = 280, 400 base points, two landmarks of every length of
+def ladder(na, top, m=280):
+    """m cameras, 400 base points, two landmarks of every length of
     ladder_lengths(na, top): a window of consecutive cameras at a random start
     and a random camera set of the same size (a window cut in two segments
     shares its cameras with its neighbours' tracks, a random set does not)."""
-    m, base_n = 280, 400
+    base_n = 400
     assert 257 <= top <= m
     rng = np.random.default_rng([na, top])
     tracks = []

@@ -10,11 +10,16 @@
 //   c++ -O3 -std=c++17 -I include -pthread tools/bench_plan.cpp
 //       bundleadjustmentmatlab_amd/csrc/ba_plan.cpp -o tools/build/bench_plan
 // Input: int32 m, n, N, then int32 obs_pt[N], int32 obs_cam[N].
+// A leading --num_a=N (6, 7, 9, 10, 12; default 6, which the pinned hashes are
+// for) plans for that camera size; the "plan" line prints the counts that
+// vlgba_plan_info reports (tests/test_schur_head_na_kinds.py holds its chunk
+// and group models to them).
 #include "../bundleadjustmentmatlab_amd/csrc/ba_plan.h"
 
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <vector>
 
 namespace {
@@ -36,8 +41,15 @@ double ms_since(std::chrono::steady_clock::time_point t)
 
 int main(int argc, char **argv)
 {
-    if (argc < 2) {
-        std::fprintf(stderr, "usage: bench_plan problem.bin [reps [problem2.bin ...]]\n");
+    // a leading --num_a=N plans for that camera size (default 6: the pinned hashes)
+    int na_arg = 6;
+    if (argc > 1 && std::strncmp(argv[1], "--num_a=", 8) == 0) {
+        na_arg = std::atoi(argv[1] + 8);
+        argv++, argc--;
+    }
+    if (argc < 2 || (na_arg != 6 && na_arg != 7 && na_arg != 9 && na_arg != 10 && na_arg != 12)) {
+        std::fprintf(stderr, "usage: bench_plan [--num_a=6|7|9|10|12] problem.bin "
+                             "[reps [problem2.bin ...]]\n");
         return 2;
     }
     const int reps = argc > 2 ? std::atoi(argv[2]) : 3;
@@ -59,13 +71,13 @@ int main(int argc, char **argv)
     vlgba_problem p{};
     p.m = m;
     p.n = n;
-    p.num_a = 6;
+    p.num_a = na_arg;
     p.num_obs = N;
     p.obs_pt = opt.data();
     p.obs_cam = ocam.data();
     p.obs_x = ox.data();
     p.K = K.data();
-    const int na = 6;
+    const int na = na_arg;
     for (int r = 0; r < reps; r++) {
         auto t0 = std::chrono::steady_clock::now();
         host_obs h;
@@ -133,6 +145,12 @@ int main(int argc, char **argv)
                     "(blocks %d, chunks %zu, groups %zu, blob %zu, fast %d)  hash %016llx\n",
                     m, n, N, t_sort, t_order, t_plan, (int)hb.jk.size() / 2, P.ch_pt.size() - 1,
                     P.grp_ch.size() - 1, P.blob.size(), fast ? 1 : 0, H.h);
+        // the counts vlgba_plan_info reports of the chunk / group plan
+        std::printf("  plan num_a %d mfma_chunks %d chunks %zu slots %zu eslots %zu words %zu "
+                    "groups %zu mfma_groups %d group_slots %zu group_eslots %zu\n",
+                    na, P.nch_mf, P.ch_pt.size() - 1, P.slot_blk.size(), P.eslot_optr.size() - 1,
+                    P.blob.size(), P.grp_ch.size() - 1, P.ngrp_mf, P.gslot_blk.size(),
+                    P.gecam.size());
     }
     }
     return 0;
