@@ -33,7 +33,7 @@
 // the sequential k_chol_seq in parity mode.
 #include "ba_internal.h"
 #include "ba_camera.h"
-#include "ba_chol_plan.h"
+#include "ba_chol.h"
 
 #include <algorithm>
 #include <atomic>
@@ -44,503 +44,25 @@
 #include <cstdlib>
 #include <vector>
 
-#define NB 64
-static_assert(NB == BA_TILE, "the kernels' tile height is the planner's");
-#define LP 66  // LDS row pitch (doubles): conflict-free 16x4 MFMA operand reads
-
-typedef double d4 __attribute__((ext_vector_type(4)));
-
-// S tile (ti, tj) -> LDS row-major T[r][c] (256 threads).  Thread (r = tid&63,
-// c0 = tid>>6) moves column c0 + 4u, u = 0..15: each wave reads whole 512-B
-// columns (coalesced) and all 16 loads are in flight before the LDS writes.
-__device__ __forceinline__ void load_tile(const double *__restrict__ S, long long lds, int ti,
-                                          int tj, double *T)
+#ifdef BA_STAMPS
+// diagnostic build: cr32_chol's two stages per workgroup (ba_chol_tile.h;
+// tools/cr_timeline.py)
+__device__ unsigned long long g_chst[8192][2];
+#define CH_ST(k)                                                                          \
+    do {                                                                                  \
+        if (threadIdx.x == 0 && blockIdx.x < 8192)                                        \
+            g_chst[blockIdx.x][k] = __builtin_amdgcn_s_memrealtime();                     \
+    } while (0)
+extern "C" int vlgba_debug_chstamps(unsigned long long *out, int nrec)
 {
-    const double *base = S + (long long)NB * ti + lds * (long long)NB * tj;
-    const int r = threadIdx.x & 63, c0 = threadIdx.x >> 6;
-    double v[16];
-#pragma unroll
-    for (int u = 0; u < 16; u++) v[u] = base[r + lds * (c0 + 4 * u)];
-#pragma unroll
-    for (int u = 0; u < 16; u++) T[r * LP + c0 + 4 * u] = v[u];
+    if (nrec > 8192) nrec = 8192;
+    return hipMemcpyFromSymbol(out, HIP_SYMBOL(g_chst), sizeof(unsigned long long) * 2 * nrec) ==
+                   hipSuccess
+               ? 0
+               : -1;
 }
-
-// S tile (ti, tj) transposed -> LDS T[c][r] = tile[r][c] (LDS writes contiguous in r)
-__device__ __forceinline__ void load_tile_t(const double *__restrict__ S, long long lds, int ti,
-                                            int tj, double *T)
-{
-    const double *base = S + (long long)NB * ti + lds * (long long)NB * tj;
-    const int r = threadIdx.x & 63, c0 = threadIdx.x >> 6;
-    double v[16];
-#pragma unroll
-    for (int u = 0; u < 16; u++) v[u] = base[r + lds * (c0 + 4 * u)];
-#pragma unroll
-    for (int u = 0; u < 16; u++) T[(c0 + 4 * u) * LP + r] = v[u];
-}
-
-// split forms of load_tile / load_tile_t: fetch to registers, then put, so
-// that several tiles' loads can be in flight together
-__device__ __forceinline__ void fetch_tile(const double *__restrict__ S, long long lds, int ti,
-                                           int tj, double v[16])
-{
-    const double *base = S + (long long)NB * ti + lds * (long long)NB * tj;
-    const int r = threadIdx.x & 63, c0 = threadIdx.x >> 6;
-#pragma unroll
-    for (int u = 0; u < 16; u++) v[u] = base[r + lds * (c0 + 4 * u)];
-}
-
-__device__ __forceinline__ void put_tile(double *T, const double v[16], bool transposed)
-{
-    const int r = threadIdx.x & 63, c0 = threadIdx.x >> 6;
-#pragma unroll
-    for (int u = 0; u < 16; u++) {
-        if (transposed)
-            T[(c0 + 4 * u) * LP + r] = v[u];
-        else
-            T[r * LP + c0 + 4 * u] = v[u];
-    }
-}
-
-typedef __attribute__((address_space(1))) unsigned long long gu64_t;
-typedef __attribute__((address_space(1))) unsigned gu32_t;
-
-template <bool SC> __device__ __forceinline__ double ldg(const double *p)
-{
-    if constexpr (SC)
-        return __builtin_bit_cast(
-            double, __hip_atomic_load((gu64_t *)p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
-    else
-        return *p;
-}
-
-template <bool SC> __device__ __forceinline__ void stg(double *p, double v)
-{
-    if constexpr (SC)
-        __hip_atomic_store((gu64_t *)p, __builtin_bit_cast(unsigned long long, v),
-                           __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    else
-        *p = v;
-}
-
-// fetch_tile / store_tile with device-coherent (sc1) accesses: tiles handed
-// between the envelope runner and the column launches running beside it
-__device__ __forceinline__ void fetch_tile_sc(const double *S, long long lds, int ti, int tj,
-                                              double v[16])
-{
-    const double *base = S + (long long)NB * ti + lds * (long long)NB * tj;
-    const int r = threadIdx.x & 63, c0 = threadIdx.x >> 6;
-#pragma unroll
-    for (int u = 0; u < 16; u++) v[u] = ldg<true>(base + r + lds * (c0 + 4 * u));
-}
-
-__device__ __forceinline__ void store_tile_sc(double *S, long long lds, int ti, int tj,
-                                              const double *T)
-{
-    double *base = S + (long long)NB * ti + lds * (long long)NB * tj;
-    const int r = threadIdx.x & 63, c0 = threadIdx.x >> 6;
-    double v[16];
-#pragma unroll
-    for (int u = 0; u < 16; u++) v[u] = T[r * LP + c0 + 4 * u];
-#pragma unroll
-    for (int u = 0; u < 16; u++) stg<true>(base + r + lds * (c0 + 4 * u), v[u]);
-}
-
-// LDS T[r][c] -> row-major 64x64 dst[r*64 + c]
-__device__ __forceinline__ void store_rowmajor(double *__restrict__ dst, const double *T)
-{
-    const int c = threadIdx.x & 63, r0 = threadIdx.x >> 6;
-    double v[16];
-#pragma unroll
-    for (int u = 0; u < 16; u++) v[u] = T[(r0 + 4 * u) * LP + c];
-#pragma unroll
-    for (int u = 0; u < 16; u++) dst[(r0 + 4 * u) * NB + c] = v[u];
-}
-
-// row-major 64x64 (src[r*64 + c]) -> LDS T[r][c], loads batched as above
-__device__ __forceinline__ void load_rowmajor(const double *__restrict__ src, double *T)
-{
-    const int c = threadIdx.x & 63, r0 = threadIdx.x >> 6;
-    double v[16];
-#pragma unroll
-    for (int u = 0; u < 16; u++) v[u] = src[(r0 + 4 * u) * NB + c];
-#pragma unroll
-    for (int u = 0; u < 16; u++) T[(r0 + 4 * u) * LP + c] = v[u];
-}
-
-__device__ __forceinline__ void store_tile(double *__restrict__ S, long long lds, int ti, int tj,
-                                           const double *T)
-{
-    double *base = S + (long long)NB * ti + lds * (long long)NB * tj;
-    const int r = threadIdx.x & 63, c0 = threadIdx.x >> 6;
-    double v[16];
-#pragma unroll
-    for (int u = 0; u < 16; u++) v[u] = T[r * LP + c0 + 4 * u];
-#pragma unroll
-    for (int u = 0; u < 16; u++) base[r + lds * (c0 + 4 * u)] = v[u];
-}
-
-// acc = As[r][:] . Bs[c][:] over K = 64 for the 64x64 tile of a 256-thread WG.
-// Wave w owns rows 32*(w>>1) .. +31, cols 32*(w&1) .. +31 as 2x2 MFMA tiles.
-// f64 16x16x4 operand map: A lane l -> A[l&15][l>>4], B lane l -> B[l>>4][l&15];
-// result register q of lane l -> (row (l>>4) + 4q, col l&15).
-__device__ __forceinline__ void mfma_64x64_acc(const double *As, const double *Bs, d4 acc[2][2])
-{
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    const int r0 = 32 * (w >> 1), c0 = 32 * (w & 1);
-    const int li = lane & 15, lk = lane >> 4;
-#pragma unroll 4
-    for (int s = 0; s < NB / 4; s++) {
-        const int kk = 4 * s + lk;
-        const double a0 = As[(r0 + li) * LP + kk];
-        const double a1 = As[(r0 + 16 + li) * LP + kk];
-        const double b0 = Bs[(c0 + li) * LP + kk];
-        const double b1 = Bs[(c0 + 16 + li) * LP + kk];
-        acc[0][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(a0, b0, acc[0][0], 0, 0, 0);
-        acc[0][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(a0, b1, acc[0][1], 0, 0, 0);
-        acc[1][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(a1, b0, acc[1][0], 0, 0, 0);
-        acc[1][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(a1, b1, acc[1][1], 0, 0, 0);
-    }
-}
-
-__device__ __forceinline__ void mfma_64x64(const double *As, const double *Bs, d4 acc[2][2])
-{
-#pragma unroll
-    for (int x = 0; x < 2; x++)
-#pragma unroll
-        for (int y = 0; y < 2; y++) acc[x][y] = d4{0.0, 0.0, 0.0, 0.0};
-    mfma_64x64_acc(As, Bs, acc);
-}
-
-// acc = A B^T over K = 64 for A = S tile (ia, kc), B = S tile (jb, kc), the
-// operands read straight from S (column-major, L2) in the 16x16x4 operand
-// layout instead of from LDS: the same MFMA chain as mfma_64x64 on the
-// loaded tiles, bit for bit, without their 64 KB of LDS.
-template <bool SCB = false>
-__device__ __forceinline__ void mfma_64x64_glb(const double *__restrict__ S, long long lds,
-                                               int ia, int jb, int kc, d4 acc[2][2])
-{
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    const int r0 = 32 * (w >> 1), c0 = 32 * (w & 1);
-    const int li = lane & 15, lk = lane >> 4;
-    const double *A = S + (long long)NB * ia + lds * (long long)NB * kc;
-    const double *B = S + (long long)NB * jb + lds * (long long)NB * kc;
-#pragma unroll
-    for (int x = 0; x < 2; x++)
-#pragma unroll
-        for (int y = 0; y < 2; y++) acc[x][y] = d4{0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-    for (int h = 0; h < 2; h++) {   // K in two halves of operand loads
-        double a0[8], a1[8], b0[8], b1[8];
-#pragma unroll
-        for (int s = 0; s < 8; s++) {
-            const long long kk = lds * (4 * (8 * h + s) + lk);
-            a0[s] = A[r0 + li + kk];
-            a1[s] = A[r0 + 16 + li + kk];
-            b0[s] = ldg<SCB>(B + c0 + li + kk);
-            b1[s] = ldg<SCB>(B + c0 + 16 + li + kk);
-        }
-#pragma unroll
-        for (int s = 0; s < 8; s++) {
-            acc[0][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(a0[s], b0[s], acc[0][0], 0, 0, 0);
-            acc[0][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(a0[s], b1[s], acc[0][1], 0, 0, 0);
-            acc[1][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(a1[s], b0[s], acc[1][0], 0, 0, 0);
-            acc[1][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(a1[s], b1[s], acc[1][1], 0, 0, 0);
-        }
-    }
-}
-
-// write acc (scale * acc + (add ? T : 0)) into LDS tile T in MFMA layout
-__device__ __forceinline__ void acc_to_lds(const d4 acc[2][2], double *T, double scale, bool add)
-{
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    const int r0 = 32 * (w >> 1), c0 = 32 * (w & 1);
-#pragma unroll
-    for (int x = 0; x < 2; x++)
-#pragma unroll
-        for (int y = 0; y < 2; y++)
-#pragma unroll
-            for (int q = 0; q < 4; q++) {
-                const int r = r0 + 16 * x + (lane >> 4) + 4 * q, c = c0 + 16 * y + (lane & 15);
-                const double v = scale * acc[x][y][q];
-                T[r * LP + c] = add ? T[r * LP + c] + v : v;
-            }
-}
-
-// ---- 16x16 MFMA helpers on LDS row-major tiles (pitch LP), one wave each ----
-// nt: acc[r][c] += sum_t A[ra+r][ka+t] * Bt[cb+c][kb+t]   (B given transposed)
-// nn: acc[r][c] += sum_t A[ra+r][ka+t] * Bn[kb+t][cb+c]
-__device__ __forceinline__ d4 mfma16_nt(const double *A, int ra, int ka, const double *Bt, int cb,
-                                        int kb, d4 acc)
-{
-    const int lane = threadIdx.x & 63, li = lane & 15, lk = lane >> 4;
-#pragma unroll
-    for (int s = 0; s < 4; s++)
-        acc = __builtin_amdgcn_mfma_f64_16x16x4f64(A[(ra + li) * LP + ka + 4 * s + lk],
-                                                   Bt[(cb + li) * LP + kb + 4 * s + lk], acc,
-                                                   0, 0, 0);
-    return acc;
-}
-
-__device__ __forceinline__ d4 mfma16_nn(const double *A, int ra, int ka, const double *Bn, int kb,
-                                        int cb, d4 acc)
-{
-    const int lane = threadIdx.x & 63, li = lane & 15, lk = lane >> 4;
-#pragma unroll
-    for (int s = 0; s < 4; s++)
-        acc = __builtin_amdgcn_mfma_f64_16x16x4f64(A[(ra + li) * LP + ka + 4 * s + lk],
-                                                   Bn[(kb + 4 * s + lk) * LP + cb + li], acc,
-                                                   0, 0, 0);
-    return acc;
-}
-
-// T[r0 + row][c0 + col] = scale * acc (+ T if add): 16x16 result layout
-__device__ __forceinline__ void put16(double *T, int r0, int c0, d4 acc, double scale, bool add)
-{
-    const int lane = threadIdx.x & 63, li = lane & 15, lk = lane >> 4;
-#pragma unroll
-    for (int q = 0; q < 4; q++) {
-        double *p = T + (r0 + lk + 4 * q) * LP + c0 + li;
-        *p = add ? *p + scale * acc[q] : scale * acc[q];
-    }
-}
-
-// out = scale * M v for a 64x64 LDS tile (row-major, pitch LP) and a 64-vector
-// in LDS, by all 256 threads: thread (row, quarter) sums 16 columns, the four
-// quarters are added in fixed order.  Result to LDS out[] (if non-null) and to
-// reg[0] of threads 0..63 (if non-null).  Ends with a barrier.
-__device__ __forceinline__ void gemv64(const double *M, const double *v, double (*part)[NB],
-                                       double *out, double scale, double *reg = nullptr)
-{
-    const int tid = threadIdx.x, row = tid & 63, qq = tid >> 6;
-    double s = 0.0;
-#pragma unroll
-    for (int c = 16 * qq; c < 16 * qq + 16; c++) s = fma(M[row * LP + c], v[c], s);
-    part[qq][row] = s;
-    __syncthreads();
-    if (tid < NB) {
-        const double t = scale * (((part[0][tid] + part[1][tid]) + part[2][tid]) + part[3][tid]);
-        if (out) out[tid] = t;
-        if (reg) reg[0] = t;
-    }
-    __syncthreads();
-}
-
-// out[c] = scale * sum_r M[r][c] v[r] (M^T v), same thread split and order as gemv64
-__device__ __forceinline__ void gemv64_t(const double *M, const double *v, double (*part)[NB],
-                                         double *out, double scale)
-{
-    const int tid = threadIdx.x, c = tid & 63, qq = tid >> 6;
-    double s = 0.0;
-#pragma unroll
-    for (int r = 16 * qq; r < 16 * qq + 16; r++) s = fma(M[r * LP + c], v[r], s);
-    part[qq][c] = s;
-    __syncthreads();
-    if (tid < NB) out[tid] = scale * (((part[0][tid] + part[1][tid]) + part[2][tid]) + part[3][tid]);
-    __syncthreads();
-}
-
-static __device__ __forceinline__ double rdlane(double v, int l)
-{
-    const long long u = __double_as_longlong(v);
-    const int lo = __builtin_amdgcn_readlane((int)(u & 0xffffffffLL), l);
-    const int hi = __builtin_amdgcn_readlane((int)(u >> 32), l);
-    return __longlong_as_double(((long long)hi << 32) | (unsigned int)lo);
-}
-
-// lane q's value to every lane of its 16-lane row (DPP row_newbcast, one
-// v_mov_b64_dpp; no SGPR round trip).  q must fold to a constant.
-template <int Q> __device__ __forceinline__ double rowbcast_c(double v)
-{
-    const long long u = __builtin_bit_cast(long long, v);
-    const long long r = __builtin_amdgcn_mov_dpp(u, 0x150 + Q, 0xf, 0xf, true);
-    return __builtin_bit_cast(double, r);
-}
-
-static __device__ __forceinline__ double rowbcast(double v, int q)
-{
-    switch (q) {
-    case 0: return rowbcast_c<0>(v);
-    case 1: return rowbcast_c<1>(v);
-    case 2: return rowbcast_c<2>(v);
-    case 3: return rowbcast_c<3>(v);
-    case 4: return rowbcast_c<4>(v);
-    case 5: return rowbcast_c<5>(v);
-    case 6: return rowbcast_c<6>(v);
-    case 7: return rowbcast_c<7>(v);
-    case 8: return rowbcast_c<8>(v);
-    case 9: return rowbcast_c<9>(v);
-    case 10: return rowbcast_c<10>(v);
-    case 11: return rowbcast_c<11>(v);
-    case 12: return rowbcast_c<12>(v);
-    case 13: return rowbcast_c<13>(v);
-    case 14: return rowbcast_c<14>(v);
-    default: return rowbcast_c<15>(v);
-    }
-}
-
-// One wave: Cholesky of the 16x16 diagonal block at (o, o) of As and its
-// inverse (lane r keeps row r of L and column r of L^-1 in registers; column
-// broadcasts by DPP, pivots by readlane).  L (zero upper) -> As, L^-1 (zero
-// upper) -> Bs.  The inverse's right-looking substitution (x_t /= L_tt,
-// x_q -= L_qt x_t) runs inside the factor loop: its step t needs only column t
-// of L, final at iteration t, and shares that column's DPP broadcasts L_qt with
-// the rank-1 update -- its FMAs fill the latency of the next pivot's rsqrt
-// chain instead of forming a second dependent loop (same operations in the
-// same order as a separate loop: bit-identical).
-__device__ __forceinline__ bool wave_factor16(double *As, double *Bs, int o)
-{
-    const int r = threadIdx.x & 63;
-    double d[16], x[16];
-#pragma unroll
-    for (int c = 0; c < 16; c++) d[c] = (r < 16) ? As[(o + r) * LP + o + c] : 0.0;
-#pragma unroll
-    for (int q = 0; q < 16; q++) x[q] = (q == r) ? 1.0 : 0.0;
-    // 1/sqrt of a pivot: hardware estimate + two Newton steps (full fp64).  No
-    // test on the chain: a pivot <= 0 (or NaN) makes its diagonal entry
-    // piv * rsq(piv) NaN, which the check after the loop finds
-    auto rsq = [&](double piv) {
-        double y = __builtin_amdgcn_rsq(piv);
-        const double hp = 0.5 * piv;
-        y = y * fma(-hp * y, y, 1.5);
-        y = y * fma(-hp * y, y, 1.5);
-        return y;
-    };
-    // pivots reach every lane of the row by a DPP broadcast (a VGPR: no
-    // readlane -> SGPR -> VALU hazard wait on the chain)
-    double y = rsq(rowbcast_c<0>(d[0]));
-#pragma unroll
-    for (int c = 0; c < 16; c++) {
-        // Unpredicated: lane c's d[c] * y is its pivot times y, the diagonal
-        // of L; lanes r < c scale / update only their upper part, which is
-        // never broadcast (broadcasts read lanes q > c) and is zeroed at the
-        // store below.
-        d[c] = d[c] * y;
-        x[c] = x[c] * y;
-        // look-ahead: column c+1 first, so the next pivot's rsqrt chain can
-        // overlap the rest of this column's rank-1 update
-        if (c + 1 < 16) {
-            const double b = rowbcast(d[c], c + 1);
-            d[c + 1] = fma(-d[c], b, d[c + 1]);
-            y = rsq(rowbcast(d[c + 1], c + 1));
-            x[c + 1] = fma(-b, x[c], x[c + 1]);
-        }
-#pragma unroll
-        for (int q = c + 2; q < 16; q++) {
-            const double b = rowbcast(d[c], q);
-            d[q] = fma(-d[c], b, d[q]);
-            x[q] = fma(-b, x[c], x[q]);
-        }
-        // keep each column's inverse updates with its broadcasts: left alone,
-        // the compiler sinks them below the loop and parks the 120 broadcasts
-        // in AGPRs until then (an empty asm that "modifies" x pins them here)
-#pragma unroll
-        for (int q = c; q < 16; q++) asm volatile("" : "+v"(x[q]));
-    }
-    double dg = 1.0;   // lane r's diagonal entry L_rr = sqrt(pivot r)
-#pragma unroll
-    for (int c = 0; c < 16; c++)
-        if (r == c) dg = d[c];
-    const bool ok = __all(r >= 16 || (dg > 0.0 && dg < __builtin_inf()));
-    if (r < 16) {
-#pragma unroll
-        for (int c = 0; c < 16; c++) As[(o + r) * LP + o + c] = (c <= r) ? d[c] : 0.0;
-#pragma unroll
-        for (int c = 0; c < 16; c++) Bs[(o + c) * LP + o + r] = x[c];
-    }
-    return ok;
-}
-
-// The 256-thread workgroup factors the 64x64 SPD tile in As (row-major, lower
-// used) and inverts the factor, blocked by 16 (blocks 0..3).  Per block column
-// k one wave factors the diagonal block (wave_factor16: L_kk and its inverse),
-// the panel blocks L_ik = A_ik Dinv_kk^T follow on the matrix pipe, then the
-// trailing blocks A_ij -= L_ik L_jk^T.  Look-ahead schedule: wave 0 updates
-// the next diagonal block first and factors it at once, while the other waves
-// finish the trailing blocks and form the off-diagonal blocks of L^-1,
-//     Li_ij = -Li_ii sum_{t=j}^{i-1} L_it Li_tj,
-// as soon as their inputs exist -- the critical path is the four diagonal
-// factorisations plus three panel steps.  Every block is formed by exactly
-// the operations of the plain right-looking order, so the result is the
-// same bit for bit.  Writes L to the lower triangle of As (the upper
-// triangle is zeroed only if zero_upper: the 16x16 blocks above the diagonal
-// keep A otherwise) and L^-1 (zero upper) to Li.  Returns false on a
-// non-positive pivot.  The caller synchronises after filling As; the result
-// is visible after return.
-__device__ __forceinline__ bool block_potrf_inv(double *As, double *Li, bool zero_upper = true)
-{
-    __shared__ double Xs[4][16 * LP];
-    __shared__ __attribute__((aligned(16))) int bad;   // keeps the static LDS a
-                                                       // multiple of 16 B (G17)
-    const int tid = threadIdx.x, w = tid >> 6;
-    // one trailing block (i, j) of block column k: A_ij -= L_ik L_jk^T
-    auto trail = [&](int i, int j, int k) {
-        d4 acc = {0.0, 0.0, 0.0, 0.0};
-        acc = mfma16_nt(As, 16 * i, 16 * k, As, 16 * j, 16 * k, acc);
-        put16(As, 16 * i, 16 * j, acc, -1.0, true);
-    };
-    // one panel block: L_ik = A_ik Dinv_kk^T
-    auto panel = [&](int i, int k) {
-        d4 acc = {0.0, 0.0, 0.0, 0.0};
-        acc = mfma16_nt(As, 16 * i, 16 * k, Li, 16 * k, 16 * k, acc);
-        put16(As, 16 * i, 16 * k, acc, 1.0, false);
-    };
-    // one off-diagonal block of the inverse, Li_ij (i > j), by wave w (> 0)
-    auto inv = [&](int i, int j) {
-        d4 acc = {0.0, 0.0, 0.0, 0.0};
-        for (int t = j; t < i; t++) acc = mfma16_nn(As, 16 * i, 16 * t, Li, 16 * t, 16 * j, acc);
-        put16(Xs[w], 0, 0, acc, 1.0, false);
-        d4 acc2 = {0.0, 0.0, 0.0, 0.0};
-        acc2 = mfma16_nn(Li, 16 * i, 16 * i, Xs[w], 0, 0, acc2);
-        put16(Li, 16 * i, 16 * j, acc2, -1.0, false);
-    };
-    auto f16 = [&](int k) {
-        if (!wave_factor16(As, Li, 16 * k) && (tid & 63) == 0) bad = 1;
-    };
-    // the six 16x16 blocks above the diagonal of L^-1 (everything else is
-    // written below); ordered before their readers by the step barriers
-    for (int q = tid; q < 6 * 256; q += blockDim.x) {
-        const int b = q >> 8, e = q & 255;
-        const int bi = b < 3 ? 0 : (b < 5 ? 1 : 2), bj = b < 3 ? b + 1 : (b < 5 ? b - 1 : 3);
-        Li[(16 * bi + (e >> 4)) * LP + 16 * bj + (e & 15)] = 0.0;
-    }
-    if (tid == 0) bad = 0;   // same wave as the writer below: program order
-#pragma unroll 1
-    for (int k = 0; k < 4; k++) {
-        // A(k): wave 0 updates diagonal block k by column k-1 and factors it;
-        // waves 1-3 apply column k-1 to the other trailing blocks
-        if (w == 0) {
-            if (k > 0) trail(k, k, k - 1);
-            f16(k);
-        } else if (k > 0) {
-            int p = 0;
-            for (int j = k; j < 4; j++)
-                for (int i = j; i < 4; i++) {
-                    if (i == k && j == k) continue;
-                    if (1 + p % 3 == w) trail(i, j, k - 1);
-                    p++;
-                }
-        }
-        __syncthreads();
-        // B(k): three tasks for waves 1-3 -- the panels of column k, then the
-        // inverse blocks of block row k
-        if (w >= 1) {
-            const int t = w - 1;
-            if (t < 3 - k)
-                panel(k + 1 + t, k);
-            else
-                inv(k, t - (3 - k));
-        }
-        __syncthreads();
-    }
-    if (zero_upper) {
-        for (int q = tid; q < NB * NB; q += blockDim.x) {   // zero the upper triangle of L
-            const int r = q >> 6, c = q & 63;
-            if (c > r) As[r * LP + c] = 0.0;
-        }
-        __syncthreads();
-    }
-    return bad == 0;
-}
+#endif
+#include "ba_chol_tile.h"
 
 // ---------------------------------------------------------------------------
 // One tile column k of the envelope Cholesky, with the trailing update of
@@ -590,13 +112,6 @@ extern "C" int vlgba_debug_fstamps(unsigned long long *out, int n)
 // an arc column leaves the separator's rhs to k_sep_update (two arcs'
 // columns run in the same launch) and its separator x separator trailing
 // pairs, which the host does not launch (they end each pair enumeration).
-// the 64 x 64 diagonal factor + inverse as two 32 x 32 factors (defined below)
-__device__ __forceinline__ bool potrf64_via32(double *As, double *Bs, double *Xs);
-
-// bounded spins of the in-launch hand-offs (then status[1]: re-solve without them)
-#ifndef BA_BACK_SPIN_MAX
-#define BA_BACK_SPIN_MAX 400000u
-#endif
 // kflag (one-launch hand-off, may be null): workgroup 0 publishes L_kk^-1 and
 // y_k (write-through stores, then flag k = epoch) and the panel workgroups
 // take them from there instead of updating and factoring A_kk themselves --
@@ -1615,386 +1130,6 @@ __global__ __launch_bounds__(256) void k_cr_update(double *__restrict__ S, long 
     }
 }
 
-// ---------------------------------------------------------------------------
-// Camera-aligned cyclic reduction on tiles of TB = NA * floor(32 / NA) rows
-// (whole cameras; S rows g = TB * tile + r, r < TB, g < ld).  A tile lives in
-// LDS as 32 x 32 (pitch LP, so the 16 x 16 MFMA helpers above apply): rows or
-// columns r >= TB, or g >= ld, are padding -- zero, with a unit diagonal in a
-// diagonal tile -- so the padded factorisation is that of the TB x TB tile
-// bordered by an identity, and padding never leaks into real entries (the
-// factors' padding rows / columns are zero off the diagonal).  Same algebra
-// and launch structure as the 64-row kernels; the pivot chain per level is
-// 32 columns instead of 64.
-// ---------------------------------------------------------------------------
-#define T32 32
-static_assert(T32 == BA_TILE32, "the camera-aligned CR's tile height is the planner's");
-
-// In-launch hand-offs of the one-launch cyclic reduction (k_cr32_fused):
-// every byte one workgroup hands to another is stored write-through (sc1,
-// 8-byte agent-scope atomic stores) and every load of it is an sc1 load
-// (8-byte agent-scope atomic loads, L1 bypassed), one workgroup per CU, the
-// flag an sc1 store after each storing wave's vmcnt(0) and a barrier: the
-// first row of MI355X_MICROARCH.md's hand-off table (no acquire fence).
-// SC = false: plain accesses (the per-level kernels, whose hand-offs cross a
-// launch boundary).
-template <bool SC = false>
-__device__ __forceinline__ void load32(const double *__restrict__ S, long long lds, int TB,
-                                       long long ld, int ti, int tj, double *T, bool transposed,
-                                       bool diag)
-{
-    const int r = threadIdx.x & 31, c0 = threadIdx.x >> 5;
-    const long long gr = (long long)TB * ti + r;
-    double v[4];
-#pragma unroll
-    for (int u = 0; u < 4; u++) {
-        const int c = c0 + 8 * u;
-        const long long gc = (long long)TB * tj + c;
-        const bool ok = r < TB && c < TB && gr < ld && gc < ld;
-        v[u] = ok ? ldg<SC>(S + gr + lds * gc) : ((diag && r == c) ? 1.0 : 0.0);
-    }
-#pragma unroll
-    for (int u = 0; u < 4; u++) {
-        const int c = c0 + 8 * u;
-        if (transposed)
-            T[c * LP + r] = v[u];
-        else
-            T[r * LP + c] = v[u];
-    }
-}
-
-template <bool SC = false>
-__device__ __forceinline__ void store32(double *__restrict__ S, long long lds, int TB,
-                                        long long ld, int ti, int tj, const double *T)
-{
-    const int r = threadIdx.x & 31, c0 = threadIdx.x >> 5;
-    const long long gr = (long long)TB * ti + r;
-#pragma unroll
-    for (int u = 0; u < 4; u++) {
-        const int c = c0 + 8 * u;
-        const long long gc = (long long)TB * tj + c;
-        if (r < TB && c < TB && gr < ld && gc < ld) stg<SC>(S + gr + lds * gc, T[r * LP + c]);
-    }
-}
-
-// 32 x 32 LDS tile <-> row-major dst[r * 32 + c]
-template <bool SC = false>
-__device__ __forceinline__ void store_rm32(double *__restrict__ dst, const double *T)
-{
-    const int c = threadIdx.x & 31, r0 = threadIdx.x >> 5;
-#pragma unroll
-    for (int u = 0; u < 4; u++) stg<SC>(dst + (r0 + 8 * u) * T32 + c, T[(r0 + 8 * u) * LP + c]);
-}
-
-template <bool SC = false>
-__device__ __forceinline__ void load_rm32(const double *__restrict__ src, double *T)
-{
-    const int c = threadIdx.x & 31, r0 = threadIdx.x >> 5;
-    double v[4];
-#pragma unroll
-    for (int u = 0; u < 4; u++) v[u] = ldg<SC>(src + (r0 + 8 * u) * T32 + c);
-#pragma unroll
-    for (int u = 0; u < 4; u++) T[(r0 + 8 * u) * LP + c] = v[u];
-}
-
-// One wave's copy of a whole 32 x 32 tile (load32 / load_rm32 with the 256
-// threads' elements on the 64 lanes of one wave: the same values at the same
-// LDS places), for the level records that wait for each operand's flag in the
-// wave that loads it (cr32_level_body's PW form)
-__device__ __forceinline__ void load32_wave(const double *__restrict__ S, long long lds, int TB,
-                                            long long ld, int ti, int tj, double *T, bool transposed,
-                                            bool diag)
-{
-    const int lane = threadIdx.x & 63, r = lane & 31, c0 = lane >> 5;
-    const long long gr = (long long)TB * ti + r;
-    double v[16];
-#pragma unroll
-    for (int u = 0; u < 16; u++) {
-        const int c = c0 + 2 * u;
-        const long long gc = (long long)TB * tj + c;
-        const bool ok = r < TB && c < TB && gr < ld && gc < ld;
-        v[u] = ok ? ldg<true>(S + gr + lds * gc) : ((diag && r == c) ? 1.0 : 0.0);
-    }
-#pragma unroll
-    for (int u = 0; u < 16; u++) {
-        const int c = c0 + 2 * u;
-        if (transposed)
-            T[c * LP + r] = v[u];
-        else
-            T[r * LP + c] = v[u];
-    }
-}
-
-__device__ __forceinline__ void load_rm32_wave(const double *__restrict__ src, double *T)
-{
-    const int lane = threadIdx.x & 63, c = lane & 31, r0 = lane >> 5;
-    double v[16];
-#pragma unroll
-    for (int u = 0; u < 16; u++) v[u] = ldg<true>(src + (r0 + 2 * u) * T32 + c);
-#pragma unroll
-    for (int u = 0; u < 16; u++) T[(r0 + 2 * u) * LP + c] = v[u];
-}
-
-// acc (one 16 x 16 block per wave: rows 16 (w >> 1), cols 16 (w & 1)) of
-// A B^T over K = 32 (nt form, as mfma_64x64)
-__device__ __forceinline__ d4 mfma32_nt(const double *A, const double *Bt, d4 acc)
-{
-    const int w = threadIdx.x >> 6, ra = 16 * (w >> 1), cb = 16 * (w & 1);
-    acc = mfma16_nt(A, ra, 0, Bt, cb, 0, acc);
-    return mfma16_nt(A, ra, 16, Bt, cb, 16, acc);
-}
-
-__device__ __forceinline__ void put32(double *T, d4 acc, double scale, bool add)
-{
-    const int w = threadIdx.x >> 6;
-    put16(T, 16 * (w >> 1), 16 * (w & 1), acc, scale, add);
-}
-
-// out[r] = scale * sum_c M[r][c] v[c] (t = 0) or sum_c M[c][r] v[c] (t = 1),
-// r < 32: thread (r, part of 4 columns), the 8 parts added in fixed order
-__device__ __forceinline__ void gemv32(const double *M, const double *v, double (*part)[T32],
-                                       double *out, bool t)
-{
-    const int tid = threadIdx.x, r = tid & 31, pq = tid >> 5;
-    double acc = 0.0;
-#pragma unroll
-    for (int c = 4 * pq; c < 4 * pq + 4; c++)
-        acc = fma(t ? M[c * LP + r] : M[r * LP + c], v[c], acc);
-    part[pq][r] = acc;
-    __syncthreads();
-    if (tid < T32)
-        out[tid] = ((((((part[0][tid] + part[1][tid]) + part[2][tid]) + part[3][tid]) +
-                     part[4][tid]) + part[5][tid]) + part[6][tid]) + part[7][tid];
-    __syncthreads();
-}
-
-// One wave: wave_factor16's Cholesky of the 16x16 diagonal block at (o, o)
-// of As, and forward substitutions z = L^-1 v of up to 48 more vectors in
-// the same loop.  Every 16-lane row of the wave holds a copy of the factor
-// rows (lane l: row l & 15), so each row's DPP broadcasts see the factor's
-// column and the copies stay bit-identical; lanes 0..15 carry the identity
-// (column r of L^-1 -> Li, if Li), lanes 16 + i (i < 16) vector i of segment
-// lo and lanes 32 + i (i < 32) vector i of segment hi (in == nullptr: none).
-// The substitutions ride on the factor's broadcasts, so a panel A L^-T (rows
-// of A as the vectors) costs no separate stage.  Every lane issues the same
-// 16 unconditional LDS loads for its start vector (e_r and zeros from a
-// small LDS row), so the loads are in flight together and need no selects.  Lanes 0..15 write L (zero upper) to As.
-// Returns false on a non-positive pivot.
-struct vseg {
-    const double *in;   // entry c of vector i: in[i * irs + c * ics]
-    double *out;        // result entry c:      out[i * ors + c * ocs]
-    int irs, ics, ors, ocs;
-    int n;              // vectors (lanes 16 / 32 + i, i < n)
-};
-
-__device__ __forceinline__ bool wave_factor16x(double *As, double *Li, int o, vseg lo, vseg hi)
-{
-    // e_r for lanes r < 16 and zeros for idle lanes come from one LDS row
-    // (ident[16] = 1), so every lane's start vector is one strided read
-    __shared__ double ident[33];
-    const int lane = threadIdx.x & 63, r = lane & 15;
-    if (lane < 33) ident[lane] = lane == 16 ? 1.0 : 0.0;
-    const bool up = lane >= 32;
-    const int idx = up ? lane - 32 : lane - 16;
-    const double *sin = up ? hi.in : lo.in;
-    const bool act = lane >= 16 && sin != nullptr && idx < (up ? hi.n : lo.n);
-    const double *pin =
-        act ? sin + idx * (up ? hi.irs : lo.irs) : (lane < 16 ? ident + 16 - r : ident);
-    const int ics = act ? (up ? hi.ics : lo.ics) : 1;
-    double d[16], x[16];
-#pragma unroll
-    for (int c = 0; c < 16; c++) d[c] = As[(o + r) * LP + o + c];
-    __builtin_amdgcn_wave_barrier();   // ident written (same wave: LDS in order)
-#pragma unroll
-    for (int q = 0; q < 16; q++) x[q] = pin[q * ics];
-    auto rsq = [&](double piv) {
-        double y = __builtin_amdgcn_rsq(piv);
-        const double hp = 0.5 * piv;
-        y = y * fma(-hp * y, y, 1.5);
-        y = y * fma(-hp * y, y, 1.5);
-        return y;
-    };
-    double y = rsq(rowbcast_c<0>(d[0]));
-#pragma unroll
-    for (int c = 0; c < 16; c++) {
-        d[c] = d[c] * y;
-        x[c] = x[c] * y;
-        if (c + 1 < 16) {
-            const double b = rowbcast(d[c], c + 1);
-            d[c + 1] = fma(-d[c], b, d[c + 1]);
-            y = rsq(rowbcast(d[c + 1], c + 1));
-            x[c + 1] = fma(-b, x[c], x[c + 1]);
-        }
-#pragma unroll
-        for (int q = c + 2; q < 16; q++) {
-            const double b = rowbcast(d[c], q);
-            d[q] = fma(-d[c], b, d[q]);
-            x[q] = fma(-b, x[c], x[q]);
-        }
-#pragma unroll
-        for (int q = c; q < 16; q++) asm volatile("" : "+v"(x[q]));
-    }
-    double dg = 1.0;
-#pragma unroll
-    for (int c = 0; c < 16; c++)
-        if (r == c) dg = d[c];
-    const bool ok = __all(lane >= 16 || (dg > 0.0 && dg < __builtin_inf()));
-    if (lane < 16) {
-#pragma unroll
-        for (int c = 0; c < 16; c++) As[(o + r) * LP + o + c] = (c <= r) ? d[c] : 0.0;
-        if (Li) {
-#pragma unroll
-            for (int c = 0; c < 16; c++) Li[(o + c) * LP + o + r] = x[c];
-        }
-    } else if (act) {
-        double *po = (up ? hi.out : lo.out) + idx * (up ? hi.ors : lo.ors);
-        const int ocs = up ? hi.ocs : lo.ocs;
-#pragma unroll
-        for (int c = 0; c < 16; c++) po[c * ocs] = x[c];
-    }
-    return ok;
-}
-
-// The 32 x 32 Cholesky of As (lower; block (0, 1) keeps A) and, if Li, L^-1
-// (row-major, zero upper) -> Li, and, if Cm, the panel Cm L^-T in place (32
-// rows), as two wave_factor16x stages with one MFMA stage between them:
-//   F0 (wave 0): L00; L10 = A10 L00^-T (lanes 16..31, in place); P0 = C0
-//      L00^-T (lanes 32..63, in place) -- or, without a panel and with rv,
-//      y0 = L00^-1 r0 (lane 32) -> yv; Li00 (lanes 0..15).  Waves 1..3 run
-//      side(w) meanwhile (work F1 needs but F0 does not, e.g. the rest of a
-//      pending update of A11 or C1).
-//   M: A11 -= L10 L10^T (wave 0); C1 -= P0 L10^T (waves 1, 2) or r1 -= L10
-//      y0 (wave 1, in rv); V = -L10 Li00 (wave 3, for Li10).
-//   F1 (wave 0): L11; P1 = C1 L11^-T (lanes 32..63) or y1 = L11^-1 r1
-//      (lane 32); Li11 (lanes 0..15); Li10 = L11^-1 V (lanes 16..31).
-// The critical path is the two 16-pivot chains plus one MFMA stage: the
-// panel and the inverse's off-diagonal block need no stage of their own.
-// The caller synchronises after filling As / Cm; results visible on return.
-#ifdef BA_STAMPS
-__device__ unsigned long long g_chst[8192][2];
-#define CH_ST(k)                                                                          \
-    do {                                                                                  \
-        if (threadIdx.x == 0 && blockIdx.x < 8192)                                        \
-            g_chst[blockIdx.x][k] = __builtin_amdgcn_s_memrealtime();                     \
-    } while (0)
-extern "C" int vlgba_debug_chstamps(unsigned long long *out, int nrec)
-{
-    if (nrec > 8192) nrec = 8192;
-    return hipMemcpyFromSymbol(out, HIP_SYMBOL(g_chst), sizeof(unsigned long long) * 2 * nrec) ==
-                   hipSuccess
-               ? 0
-               : -1;
-}
-#else
-#define CH_ST(k)
-#endif
-
-template <class Side>
-__device__ __forceinline__ bool cr32_chol(double *As, double *Li, double *Cm, double *Xs,
-                                          double *rv, double *yv, Side side)
-{
-    __shared__ int bad32;
-    const int tid = threadIdx.x, w = tid >> 6;
-    if (Li) Li[(tid >> 4) * LP + 16 + (tid & 15)] = 0.0;   // block (0, 1) of L^-1
-    if (w == 0) {
-        const vseg lo{As + 16 * LP, As + 16 * LP, LP, 1, LP, 1, 16};   // A10 rows -> L10
-        const vseg hi = Cm ? vseg{Cm, Cm, LP, 1, LP, 1, 32}            // C0 rows -> P0
-                           : vseg{rv, yv, 0, 1, 0, 1, 1};              // or r0 -> y0
-        const bool ok = wave_factor16x(As, Li, 0, lo, hi);
-        if (tid == 0) bad32 = ok ? 0 : 1;
-    } else {
-        side(w);
-    }
-    __syncthreads();
-    CH_ST(0);
-    if (w == 0) {   // A11 -= L10 L10^T
-        d4 acc = {0.0, 0.0, 0.0, 0.0};
-        acc = mfma16_nt(As, 16, 0, As, 16, 0, acc);
-        put16(As, 16, 16, acc, -1.0, true);
-    } else if (w <= 2) {   // C1 -= P0 L10^T, rows 16 (w - 1) ..
-        if (Cm) {
-            d4 acc = {0.0, 0.0, 0.0, 0.0};
-            acc = mfma16_nt(Cm, 16 * (w - 1), 0, As, 16, 0, acc);
-            put16(Cm, 16 * (w - 1), 16, acc, -1.0, true);
-        } else if (rv && w == 1 && (tid & 63) < 16) {   // r1' = r1 - L10 y0
-            const int r = tid & 63;
-            double t = 0.0;
-#pragma unroll
-            for (int c = 0; c < 16; c++) t = fma(As[(16 + r) * LP + c], yv[c], t);
-            rv[16 + r] = rv[16 + r] - t;
-        }
-    } else if (Li) {   // V = -L10 Li00
-        d4 acc = {0.0, 0.0, 0.0, 0.0};
-        acc = mfma16_nn(As, 16, 0, Li, 0, 0, acc);
-        put16(Xs, 0, 0, acc, -1.0, false);
-    }
-    __syncthreads();
-    CH_ST(1);
-    if (w == 0) {
-        // V's columns -> Li10's columns; C1 rows -> P1, or r1' -> y1
-        const vseg lo{Li ? Xs : nullptr, Li ? Li + 16 * LP : nullptr, 1, LP, 1, LP, 16};
-        const vseg hi = Cm ? vseg{Cm + 16, Cm + 16, LP, 1, LP, 1, 32}
-                           : vseg{rv ? rv + 16 : nullptr, yv ? yv + 16 : nullptr, 0, 1, 0, 1, 1};
-        const bool ok = wave_factor16x(As, Li, 16, lo, hi);
-        if (tid == 0 && !ok) bad32 = 1;
-    }
-    __syncthreads();
-    return bad32 == 0;
-}
-
-// The envelope's 64 x 64 diagonal factor and L^-1 (row-major, zero upper, in
-// Bs) as two cr32_chol factors: F(A00) -> L00, Li00 and the panel L10 = A10
-// L00^-T on the same pivot chains; then A11 -= L10 L10^T (waves 0-2, its
-// three lower 16-blocks) beside T = L10 Li00 (into Bs's block (1, 0)); F(A11)
-// -> L11, Li11; Li10 = -Li11 T.  Two 32-row factors (~8.2k cycles each,
-// profiles/r04c_ubench_cr32.txt) instead of four dependent 16-row stages with
-// their updates in between (block_potrf_inv, ~29.5k cycles).  Xs: 16 x LP
-// scratch.  Ends with a barrier.
-__device__ __forceinline__ bool potrf64_via32(double *As, double *Bs, double *Xs)
-{
-    const int tid = threadIdx.x, w = tid >> 6;
-    for (int q = tid; q < 32 * 32; q += blockDim.x) Bs[(q >> 5) * LP + 32 + (q & 31)] = 0.0;
-    bool ok = cr32_chol(As, Bs, As + 32 * LP, Xs, nullptr, nullptr, [](int) {});
-    {
-        // A11 -= L10 L10^T: blocks (32, 32), (48, 32), (48, 48) by waves 0..2;
-        // T = L10 Li00 blocks (32 + 16 (u >> 1), 16 (u & 1)), u = w and w + 4 - 1 ...
-        const int ri = w == 0 ? 32 : 48, ci = w == 2 ? 48 : 32;
-        d4 acc = {0.0, 0.0, 0.0, 0.0};
-        if (w < 3) {
-            acc = mfma16_nt(As, ri, 0, As, ci, 0, acc);
-            acc = mfma16_nt(As, ri, 16, As, ci, 16, acc);
-        }
-        // T blocks: wave 3 takes (32, 0) and (32, 16), waves 0 / 1 take (48, 0) / (48, 16)
-        d4 t0 = {0.0, 0.0, 0.0, 0.0}, t1 = {0.0, 0.0, 0.0, 0.0};
-        if (w == 3) {
-            t0 = mfma16_nn(As, 32, 0, Bs, 0, 0, t0);
-            t0 = mfma16_nn(As, 32, 16, Bs, 16, 0, t0);
-            t1 = mfma16_nn(As, 32, 16, Bs, 16, 16, t1);   // Li00 block (0, 1) is zero
-        } else if (w < 2) {
-            t0 = mfma16_nn(As, 48, 0, Bs, 0, 16 * w, t0);
-            t0 = mfma16_nn(As, 48, 16, Bs, 16, 16 * w, t0);
-        }
-        if (w < 3) put16(As, ri, ci, acc, -1.0, true);
-        if (w == 3) {
-            put16(Bs, 32, 0, t0, 1.0, false);
-            put16(Bs, 32, 16, t1, 1.0, false);
-        } else if (w < 2) {
-            put16(Bs, 48, 16 * w, t0, 1.0, false);
-        }
-    }
-    __syncthreads();
-    ok = cr32_chol(As + 32 * LP + 32, Bs + 32 * LP + 32, nullptr, Xs, nullptr, nullptr,
-                   [](int) {}) && ok;
-    {   // Li10 = -Li11 T, block (32 + 16 (w >> 1), 16 (w & 1)) by wave w
-        const int ri = 32 + 16 * (w >> 1), cj = 16 * (w & 1);
-        d4 acc = {0.0, 0.0, 0.0, 0.0};
-        acc = mfma16_nn(Bs, ri, 32, Bs, 32, cj, acc);
-        acc = mfma16_nn(Bs, ri, 48, Bs, 48, cj, acc);
-        __syncthreads();
-        put16(Bs, ri, cj, acc, -1.0, false);
-    }
-    __syncthreads();
-    return ok;
-}
 
 // LDS of one cyclic-reduction record: five 32-row tiles, the 16-row scratch
 // of potrf32_inv, five 32-vectors and the gemv partials.  The per-level
@@ -3168,28 +2303,10 @@ int ba_chol_setup(ba_dev *d, const int *blk_jk, int nb)
                                 env_is("VLGBA_ND", 'v'), !env_is("VLGBA_ND_GROUPED", '0'),
                                 env_is("VLGBA_ENV_RUNNER", '1')};
     const chol_plan_in in = {d->m, d->na, d->ld, d->lds, d->ncu, d->dense_solve, blk_jk, nb, opt};
-    d->plan = new chol_plan;
-    const chol_plan &P = *d->plan;
-    TRY_RC(chol_plan_build(in, *d->plan));
-    // the scalars the other files read
-    d->nt = P.nt;
-    d->n_env = P.n_env();
-    d->cr_nlev = P.cr_nlev;
-    d->cr32 = P.cr32;
-    d->tb32 = P.tb32;
-    d->nt32 = P.nt32;
-    d->asm_direct_ok = P.asm_direct_ok;
-    d->cr_fused = P.cr_fused;
-    d->nd_np = P.nd_np;
-    d->nd_grouped = P.nd_grouped;
-    for (int t = 0; t <= BA_ND_MAX; t++) d->nd_a0[t] = P.nd_a0[t];
-    if (P.nd_np > 0) d->slds = P.slds;
-    d->nd_npair = P.nd_npair;
-    d->nd_nrec = P.nd_nrec;
-    d->fl_factor = P.fl_factor;
-    d->fl_syrk = P.fl_syrk;
-    d->fl_back = P.fl_back;
-    d->env_runner = P.env_runner;
+    ba_chol *c = d->chol = new ba_chol();   // (zeroed: null pointers, epochs 0)
+    const chol_plan &P = c->plan;
+    TRY_RC(chol_plan_build(in, c->plan));
+    c->env_runner = P.env_runner;
 
     const int nt = P.nt;
     auto put = [&](int *dst, const std::vector<int> &v) -> int {   // (nothing when empty)
@@ -3201,127 +2318,121 @@ int ba_chol_setup(ba_dev *d, const int *blk_jk, int nb)
     if (P.cr_nlev > 0) {   // cyclic reduction: its records, L(p, e) | L(q, e)
         const int ntc = P.cr_tiles();
         if (P.cr32) {
-            TRY_RC(dev_alloc(&d->xgran, sizeof(unsigned long long) * 64 * (size_t)ntc));
-            VLGBA_CHECK(hipMemsetAsync(d->xgran, 0, sizeof(unsigned long long) * 64 * (size_t)ntc,
+            TRY_RC(dev_alloc(&c->xgran, sizeof(unsigned long long) * 64 * (size_t)ntc));
+            VLGBA_CHECK(hipMemsetAsync(c->xgran, 0, sizeof(unsigned long long) * 64 * (size_t)ntc,
                                        d->stream));
-            d->back_epoch = 0;
             if (P.cr_fused) {
                 const size_t nfl = (size_t)5 * P.cr_nlev * ntc;
-                TRY_RC(dev_alloc(&d->crflag, sizeof(unsigned) * nfl));
-                VLGBA_CHECK(hipMemsetAsync(d->crflag, 0, sizeof(unsigned) * nfl, d->stream));
+                TRY_RC(dev_alloc(&c->crflag, sizeof(unsigned) * nfl));
+                VLGBA_CHECK(hipMemsetAsync(c->crflag, 0, sizeof(unsigned) * nfl, d->stream));
             }
-            TRY_RC(dev_alloc(&d->crf, sizeof(int) * (P.frec.size() + 1)));
-            TRY_RC(dev_alloc(&d->crs, sizeof(int) * (P.srec.size() + 1)));
-            TRY_RC(put(d->crf, P.frec));
-            TRY_RC(put(d->crs, P.srec));
+            TRY_RC(dev_alloc(&c->crf, sizeof(int) * (P.frec.size() + 1)));
+            TRY_RC(dev_alloc(&c->crs, sizeof(int) * (P.srec.size() + 1)));
+            TRY_RC(put(c->crf, P.frec));
+            TRY_RC(put(c->crs, P.srec));
             VLGBA_CHECK(hipStreamSynchronize(d->stream));
         }
-        TRY_RC(dev_alloc(&d->cr_elim, sizeof(int) * P.elim.size()));
-        TRY_RC(dev_alloc(&d->cr_keep, sizeof(int) * (P.keep.size() + 1)));
-        TRY_RC(dev_alloc(&d->crL, sizeof(double) * 2 * (size_t)ntc *
+        TRY_RC(dev_alloc(&c->cr_elim, sizeof(int) * P.elim.size()));
+        TRY_RC(dev_alloc(&c->cr_keep, sizeof(int) * (P.keep.size() + 1)));
+        TRY_RC(dev_alloc(&c->crL, sizeof(double) * 2 * (size_t)ntc *
                                       (P.cr32 ? T32 * T32 : NB * NB)));
-        TRY_RC(put(d->cr_elim, P.elim));
-        TRY_RC(put(d->cr_keep, P.keep));
+        TRY_RC(put(c->cr_elim, P.elim));
+        TRY_RC(put(c->cr_keep, P.keep));
     }
     // per envelope tile: the co-visible blocks (j >= k) overlapping it
-    TRY_RC(dev_alloc(&d->tb_ptr, sizeof(int) * P.tptr.size()));
-    TRY_RC(dev_alloc(&d->tb_blk, sizeof(int) * (P.tblk.size() + 1)));
-    TRY_RC(put(d->tb_ptr, P.tptr));
-    TRY_RC(put(d->tb_blk, P.tblk));
+    TRY_RC(dev_alloc(&c->tb_ptr, sizeof(int) * P.tptr.size()));
+    TRY_RC(dev_alloc(&c->tb_blk, sizeof(int) * (P.tblk.size() + 1)));
+    TRY_RC(put(c->tb_ptr, P.tptr));
+    TRY_RC(put(c->tb_blk, P.tblk));
     VLGBA_CHECK(hipStreamSynchronize(d->stream));
     // the factor's storage: S (dense, column major), the diagonal tiles'
     // inverses, the forward-solve result (+ the 32-row CR's last tile)
     const bool nd = P.nd_np > 0;
     const long long sdim = nd ? P.slds : d->lds;
-    TRY_RC(dev_alloc(&d->S, sizeof(double) * (size_t)(sdim * sdim)));
-    TRY_RC(dev_alloc(&d->linv, sizeof(double) * (size_t)(sdim / NB) * NB * NB));
-    TRY_RC(dev_alloc(&d->ywork, sizeof(double) * (size_t)(sdim + NB)));
+    TRY_RC(dev_alloc(&c->S, sizeof(double) * (size_t)(sdim * sdim)));
+    TRY_RC(dev_alloc(&c->linv, sizeof(double) * (size_t)(sdim / NB) * NB * NB));
+    TRY_RC(dev_alloc(&c->ywork, sizeof(double) * (size_t)(sdim + NB)));
     if (nd) {
         auto up = [&](int **dst, const std::vector<int> &v) -> int {
             TRY_RC(dev_alloc(dst, sizeof(int) * (v.size() + 1)));
             return put(*dst, v);
         };
-        TRY_RC(up(&d->nd_crow, P.crow));
-        TRY_RC(up(&d->nd_prow, P.prow));
-        TRY_RC(up(&d->nd_rowsrc, P.rowsrc));
-        TRY_RC(up(&d->nd_pair, P.pairs));
-        TRY_RC(up(&d->nd_pptr, P.pptr));
-        TRY_RC(up(&d->nd_rec, P.rec));
-        TRY_RC(up(&d->nd_klist, P.klist));
-        TRY_RC(dev_alloc(&d->nd_rhs, sizeof(double) * (size_t)P.slds));
-        TRY_RC(dev_alloc(&d->nd_x, sizeof(double) * (size_t)P.slds));
-        TRY_RC(dev_alloc(&d->nd_part, sizeof(double) * ((size_t)P.nd_nrec + 1) * (NB * NB + NB)));
+        TRY_RC(up(&c->nd_crow, P.crow));
+        TRY_RC(up(&c->nd_prow, P.prow));
+        TRY_RC(up(&c->nd_rowsrc, P.rowsrc));
+        TRY_RC(up(&c->nd_pair, P.pairs));
+        TRY_RC(up(&c->nd_pptr, P.pptr));
+        TRY_RC(up(&c->nd_rec, P.rec));
+        TRY_RC(up(&c->nd_klist, P.klist));
+        TRY_RC(dev_alloc(&c->nd_rhs, sizeof(double) * (size_t)P.slds));
+        TRY_RC(dev_alloc(&c->nd_x, sizeof(double) * (size_t)P.slds));
+        TRY_RC(dev_alloc(&c->nd_part, sizeof(double) * ((size_t)P.nd_nrec + 1) * (NB * NB + NB)));
         VLGBA_CHECK(hipStreamSynchronize(d->stream));
     }
-    TRY_RC(dev_alloc(&d->pan_list, sizeof(int) * (P.pan_list.size() + 1)));
+    TRY_RC(dev_alloc(&c->pan_list, sizeof(int) * (P.pan_list.size() + 1)));
     if (P.back_one_launch) {
-        TRY_RC(dev_alloc(&d->pan_ptr, sizeof(int) * (nt + 1)));
-        TRY_RC(put(d->pan_ptr, P.pan_ptr));
-        TRY_RC(dev_alloc(&d->xgran64, sizeof(unsigned long long) * 128 * (size_t)nt));
-        VLGBA_CHECK(hipMemsetAsync(d->xgran64, 0, sizeof(unsigned long long) * 128 * (size_t)nt,
+        TRY_RC(dev_alloc(&c->pan_ptr, sizeof(int) * (nt + 1)));
+        TRY_RC(put(c->pan_ptr, P.pan_ptr));
+        TRY_RC(dev_alloc(&c->xgran64, sizeof(unsigned long long) * 128 * (size_t)nt));
+        VLGBA_CHECK(hipMemsetAsync(c->xgran64, 0, sizeof(unsigned long long) * 128 * (size_t)nt,
                                    d->stream));
-        d->back_epoch = 0;
     }
     if (P.handoff) {   // the factor's in-launch hand-off
-        TRY_RC(dev_alloc(&d->kflag, sizeof(unsigned) * (size_t)nt));
-        VLGBA_CHECK(hipMemsetAsync(d->kflag, 0, sizeof(unsigned) * (size_t)nt, d->stream));
-        d->fac_epoch = 0;
+        TRY_RC(dev_alloc(&c->kflag, sizeof(unsigned) * (size_t)nt));
+        VLGBA_CHECK(hipMemsetAsync(c->kflag, 0, sizeof(unsigned) * (size_t)nt, d->stream));
         // runner mode's flags: lflag | dflag | uflag | pflag, nt each, then
         // the runner's timeout word.  Opt-in (VLGBA_ENV_RUNNER=1): the runner
         // makes progress only while its stream has a hardware queue of its own
         if (P.runner_flags) {
             const size_t nw = 4 * (size_t)nt + 1;
-            TRY_RC(dev_alloc(&d->rflag, sizeof(unsigned) * nw));
-            VLGBA_CHECK(hipMemsetAsync(d->rflag, 0, sizeof(unsigned) * nw, d->stream));
+            TRY_RC(dev_alloc(&c->rflag, sizeof(unsigned) * nw));
+            VLGBA_CHECK(hipMemsetAsync(c->rflag, 0, sizeof(unsigned) * nw, d->stream));
         }
     }
-    TRY_RC(dev_alloc(&d->env_tiles, sizeof(int) * (P.env.size() + 1)));
-    TRY_RC(put(d->pan_list, P.pan_list));
-    VLGBA_CHECK(hipMemcpyAsync(d->env_tiles, P.env.data(), sizeof(int) * P.env.size(),
+    TRY_RC(dev_alloc(&c->env_tiles, sizeof(int) * (P.env.size() + 1)));
+    TRY_RC(put(c->pan_list, P.pan_list));
+    VLGBA_CHECK(hipMemcpyAsync(c->env_tiles, P.env.data(), sizeof(int) * P.env.size(),
                                hipMemcpyHostToDevice, d->stream));
-    VLGBA_CHECK(hipMemsetAsync(d->S, 0, sizeof(double) * sdim * sdim, d->stream));
+    VLGBA_CHECK(hipMemsetAsync(c->S, 0, sizeof(double) * sdim * sdim, d->stream));
     VLGBA_CHECK(hipStreamSynchronize(d->stream));
     return 0;
 }
 
-// also after a setup that returned early: every pointer is null or owned
+// also after a setup that returned early (every device pointer of *d->chol is
+// null or owned) and for a context that was never set up (stage mode:
+// d->chol is null).  The runner's stream is the process's (env_runner_stream)
 void ba_chol_free(ba_dev *d)
 {
-    void **dev[] = {(void **)&d->S, (void **)&d->linv, (void **)&d->ywork, (void **)&d->nd_crow,
-                    (void **)&d->nd_prow, (void **)&d->nd_rowsrc, (void **)&d->nd_rhs,
-                    (void **)&d->nd_x, (void **)&d->nd_pair, (void **)&d->nd_pptr,
-                    (void **)&d->nd_rec, (void **)&d->nd_klist, (void **)&d->nd_part,
-                    (void **)&d->xgran, (void **)&d->rflag, (void **)&d->crflag, (void **)&d->crf,
-                    (void **)&d->crs, (void **)&d->cr_elim, (void **)&d->cr_keep, (void **)&d->crL,
-                    (void **)&d->tb_ptr, (void **)&d->tb_blk, (void **)&d->pan_list,
-                    (void **)&d->pan_ptr, (void **)&d->xgran64, (void **)&d->kflag,
-                    (void **)&d->env_tiles};
-    for (void **q : dev) {
-        if (*q) ba_dfree(*q);
-        *q = nullptr;
-    }
-    delete d->plan;
-    d->plan = nullptr;
-    d->nd_np = 0;
-    d->cr_fused = 0;
-    d->cr_nlev = 0;
-    d->rstream = nullptr;   // the process's (env_runner_stream)
+    ba_chol *c = d->chol;
+    if (!c) return;
+    void *dev[] = {c->S,       c->linv,     c->ywork,  c->nd_crow, c->nd_prow, c->nd_rowsrc,
+                   c->nd_rhs,  c->nd_x,     c->nd_pair, c->nd_pptr, c->nd_rec, c->nd_klist,
+                   c->nd_part, c->xgran,    c->rflag,  c->crflag,  c->crf,     c->crs,
+                   c->cr_elim, c->cr_keep,  c->crL,    c->tb_ptr,  c->tb_blk,  c->pan_list,
+                   c->pan_ptr, c->xgran64,  c->kflag,  c->env_tiles};
+    for (void *q : dev)
+        if (q) ba_dfree(q);
+    delete c;
+    d->chol = nullptr;
 }
 
 int ba_assemble_tiles(ba_dev *d)
 {
     if (d->asm_direct) return 0;   // k_schur_reduce wrote S (and reset the status)
-    const bool nd = d->nd_np > 0;
-    k_assemble_tiles<<<d->n_env, 256, 0, d->stream>>>(
-        d->S, nd ? d->slds : d->lds, d->env_tiles, d->tb_ptr, d->tb_blk, d->blk_jk, d->sblk, d->na,
-        nd ? d->slds : d->ld, nd ? d->nd_rhs : d->rhs, d->scal + 4, nd ? d->nd_crow : nullptr,
-        nd ? d->nd_rowsrc : nullptr, d->rhs);
+    const ba_chol *c = d->chol;
+    const bool nd = c->plan.nd_np > 0;
+    const long long slds = c->plan.slds;
+    k_assemble_tiles<<<c->plan.n_env(), 256, 0, d->stream>>>(
+        c->S, nd ? slds : d->lds, c->env_tiles, c->tb_ptr, c->tb_blk, d->blk_jk, d->sblk, d->na,
+        nd ? slds : d->ld, nd ? c->nd_rhs : d->rhs, d->scal + 4, nd ? c->nd_crow : nullptr,
+        nd ? c->nd_rowsrc : nullptr, d->rhs);
     return -(int)hipGetLastError();
 }
 
 int ba_chol_prepare(ba_dev *d)
 {
-    k_zero_env<<<d->n_env, 256, 0, d->stream>>>(d->S, d->lds, d->env_tiles);
+    const ba_chol *c = d->chol;
+    k_zero_env<<<c->plan.n_env(), 256, 0, d->stream>>>(c->S, d->lds, c->env_tiles);
     return -(int)hipGetLastError();
 }
 
@@ -3335,7 +2446,8 @@ int ba_fix_diag_plain(ba_dev *d, double *S, long long ld)
 
 int ba_chol_fix_diag(ba_dev *d)
 {
-    k_fix_diag<<<(int)((d->lds + 255) / 256), 256, 0, d->stream>>>(d->S, d->rhs, d->lds);
+    k_fix_diag<<<(int)((d->lds + 255) / 256), 256, 0, d->stream>>>(d->chol->S, d->rhs,
+                                                                    d->lds);
     return -(int)hipGetLastError();
 }
 
@@ -3347,14 +2459,15 @@ int ba_chol_fix_diag(ba_dev *d)
 // behind it on a shared queue every wait times out)
 int ba_env_runner_timed_out(ba_dev *d)
 {
-    if (!d->env_runner || !d->rflag) return 0;
-    unsigned *rto = d->rflag + 4 * (size_t)d->nt;
+    ba_chol *c = d->chol;   // (a solving context: never null here)
+    if (!c->env_runner || !c->rflag) return 0;
+    unsigned *rto = c->rflag + 4 * (size_t)c->plan.nt;
     unsigned h = 0;
     if (hipMemcpyAsync(&h, rto, sizeof h, hipMemcpyDeviceToHost, d->stream) != hipSuccess ||
         hipStreamSynchronize(d->stream) != hipSuccess)
         return -1;
     if (!h) return 0;
-    d->env_runner = 0;
+    c->env_runner = 0;
     std::fprintf(stderr, "[vlgba] envelope runner off for this context: one of its hand-offs "
                          "timed out (its stream shares a hardware queue?)\n");
     return 1;
@@ -3392,12 +2505,13 @@ static hipStream_t env_runner_stream()
 
 static bool env_run_on(ba_dev *d, const unsigned *kflag, int ncols)
 {
-    if (!(d->env_runner && kflag && d->pan_ptr && d->rflag && !(d->kt && d->kt->on) &&
+    ba_chol *c = d->chol;
+    if (!(c->env_runner && kflag && c->pan_ptr && c->rflag && !(d->kt && d->kt->on) &&
           ncols >= env_run_min()))
         return false;
-    if (!d->rstream) d->rstream = env_runner_stream();
-    if (!d->rstream) {
-        d->env_runner = 0;
+    if (!c->rstream) c->rstream = env_runner_stream();
+    if (!c->rstream) {
+        c->env_runner = 0;
         return false;
     }
     return true;
@@ -3405,9 +2519,10 @@ static bool env_run_on(ba_dev *d, const unsigned *kflag, int ncols)
 
 static env_rm env_rm_of(const ba_dev *d, int kend)
 {
-    if (!d->rflag) return env_rm{};
-    return env_rm{d->rflag, d->rflag + d->nt, d->rflag + 2 * (size_t)d->nt,
-                  d->rflag + 3 * (size_t)d->nt, d->rflag + 4 * (size_t)d->nt, kend};
+    unsigned *rflag = d->chol->rflag;
+    const size_t nt = (size_t)d->chol->plan.nt;
+    if (!rflag) return env_rm{};
+    return env_rm{rflag, rflag + nt, rflag + 2 * nt, rflag + 3 * nt, rflag + 4 * nt, kend};
 }
 
 // fork the side stream off the library stream and start the runner there.
@@ -3415,20 +2530,21 @@ static env_rm env_rm_of(const ba_dev *d, int kend)
 // or the launch failed (the error is returned).
 static int env_runner_start(ba_dev *d, const env_runs &Rn, long long L, double *rhs)
 {
-    if (d->debug_runner_fail > 0) {   // vlgba_debug_force_status word 6
-        d->debug_runner_fail--;
+    ba_chol *c = d->chol;
+    if (c->debug_runner_fail > 0) {   // vlgba_debug_force_status word 6
+        c->debug_runner_fail--;
         return -(int)hipErrorLaunchFailure;
     }
     const size_t smem4 = sizeof(double) * 4 * NB * LP;
     TRY_RC(ba_ensure_dyn_lds((const void *)k_env_runner, smem4));
     VLGBA_CHECK(hipEventRecord(d->ev_fork, d->stream));
-    VLGBA_CHECK(hipStreamWaitEvent(d->rstream, d->ev_fork, 0));
-    k_env_runner<<<Rn.np, 256, smem4, d->rstream>>>(d->S, L, d->pan_ptr, d->pan_list, Rn,
-                                                    d->linv, rhs, d->ywork, d->scal + 4,
-                                                    d->kflag, env_rm_of(d, 0), d->fac_epoch);
+    VLGBA_CHECK(hipStreamWaitEvent(c->rstream, d->ev_fork, 0));
+    k_env_runner<<<Rn.np, 256, smem4, c->rstream>>>(c->S, L, c->pan_ptr, c->pan_list, Rn,
+                                                    c->linv, rhs, c->ywork, d->scal + 4,
+                                                    c->kflag, env_rm_of(d, 0), c->fac_epoch);
     TRY_RC(-(int)hipGetLastError());
-    VLGBA_CHECK(hipEventRecord(d->ev_join, d->rstream));
-    d->runner_runs++;
+    VLGBA_CHECK(hipEventRecord(d->ev_join, c->rstream));
+    c->runner_runs++;
     return 0;
 }
 
@@ -3438,6 +2554,7 @@ static int env_runner_start(ba_dev *d, const env_runs &Rn, long long L, double *
 static int envelope_columns(ba_dev *d, int k0, int k1, long long L, double *rhs,
                             unsigned *kflag)
 {
+    ba_chol *c = d->chol;
     // two LDS tiles with the hand-off (two workgroups per CU), three without
     const size_t smem3 = sizeof(double) * 3 * NB * LP, smem2 = sizeof(double) * 2 * NB * LP;
     bool run = k1 > k0 && env_run_on(d, kflag, k1 - k0);
@@ -3448,7 +2565,7 @@ static int envelope_columns(ba_dev *d, int k0, int k1, long long L, double *rhs,
         Rn.k1[0] = k1;
         if (env_runner_start(d, Rn, L, rhs)) run = false;
     }
-    const std::vector<int> &pan_ptr = d->plan->pan_ptr, &pan_list = d->plan->pan_list;
+    const std::vector<int> &pan_ptr = c->plan.pan_ptr, &pan_list = c->plan.pan_list;
     for (int k = k0; k < k1; k++) {
         const int p0 = pan_ptr[k], T = pan_ptr[k + 1] - p0;
         const int q0 = k > k0 ? pan_ptr[k - 1] : 0, Tp = k > k0 ? p0 - q0 : 0;
@@ -3458,8 +2575,8 @@ static int envelope_columns(ba_dev *d, int k0, int k1, long long L, double *rhs,
         const int nw = ntr;   // one workgroup per trailing pair
         KT_B(d);
         k_factor_step<<<1 + T + nw, 256, kflag ? smem2 : smem3, d->stream>>>(
-            d->S, L, k, d->pan_list + p0, T, d->pan_list + q0, Tp, d->linv, rhs, d->ywork,
-            d->scal + 4, kflag, d->fac_epoch, ntr, nw, env_rm_of(d, run ? k1 : 0));
+            c->S, L, k, c->pan_list + p0, T, c->pan_list + q0, Tp, c->linv, rhs, c->ywork,
+            d->scal + 4, kflag, c->fac_epoch, ntr, nw, env_rm_of(d, run ? k1 : 0));
         KT_E(d, KT_FACTOR);
     }
     if (run) VLGBA_CHECK(hipStreamWaitEvent(d->stream, d->ev_join, 0));
@@ -3469,22 +2586,23 @@ static int envelope_columns(ba_dev *d, int k0, int k1, long long L, double *rhs,
 // x = L^-T y of the envelope factor (ywork holds y; consumed)
 static int envelope_backward(ba_dev *d, long long L, double *x, int nospin)
 {
-    const int nt = d->nt;
-    if (d->xgran64 && !nospin) {   // every column co-resident: the backward solve in one launch
-        if (++d->back_epoch == 0) d->back_epoch = 1;
+    ba_chol *c = d->chol;
+    const int nt = c->plan.nt;
+    if (c->xgran64 && !nospin) {   // every column co-resident: the backward solve in one launch
+        if (++c->back_epoch == 0) c->back_epoch = 1;
         const size_t smem2 = sizeof(double) * 2 * NB * LP;
         TRY_RC(ba_ensure_dyn_lds((const void *)k_backward_all, smem2));
         KT_B(d);
-        k_backward_all<<<nt, 256, smem2, d->stream>>>(d->S, L, nt, d->pan_ptr, d->pan_list,
-                                                       d->linv, d->ywork, x, d->xgran64,
-                                                       d->back_epoch, d->scal + 4);
+        k_backward_all<<<nt, 256, smem2, d->stream>>>(c->S, L, nt, c->pan_ptr, c->pan_list,
+                                                       c->linv, c->ywork, x, c->xgran64,
+                                                       c->back_epoch, d->scal + 4);
         KT_E(d, KT_BACKWARD);
         return -(int)hipGetLastError();
     }
     for (int k = nt - 1; k >= 0; k--) {
-        const int j0 = d->plan->tfirst[k];
+        const int j0 = c->plan.tfirst[k];
         KT_B(d);
-        k_backward<<<k - j0 + 1, 256, 0, d->stream>>>(d->S, L, k, j0, d->linv, d->ywork, x);
+        k_backward<<<k - j0 + 1, 256, 0, d->stream>>>(c->S, L, k, j0, c->linv, c->ywork, x);
         KT_E(d, KT_BACKWARD);
     }
     return -(int)hipGetLastError();
@@ -3496,27 +2614,28 @@ static int envelope_backward(ba_dev *d, long long L, double *x, int nospin)
 // vlgba_covariance, which runs no back substitution after it)
 int ba_cr32_factor(ba_dev *d)
 {
-    const std::vector<int> &eptr = d->plan->eptr;
-    const std::vector<int> &fptr = d->plan->fptr, &sptr = d->plan->sptr;
+    ba_chol *c = d->chol;
+    const std::vector<int> &eptr = c->plan.eptr;
+    const std::vector<int> &fptr = c->plan.fptr, &sptr = c->plan.sptr;
     const int ncu32 = d->ncu;
-    const int n32 = d->nt32, TB = d->tb32;
+    const int n32 = c->plan.nt32, TB = c->plan.tb32;
     {   // level 0 on the assembled S
         const int ne = eptr[1];
         const int fs = 3 * ne <= 2 * ncu32;   // ~60 KB LDS: two workgroups per CU
         KT_B(d);
         k_cr32_factor<<<fs ? 3 * ne : ne, 256, 0, d->stream>>>(
-            d->S, d->lds, TB, d->ld, d->cr_elim, n32, d->linv, d->crL, d->rhs, d->ywork,
+            c->S, d->lds, TB, d->ld, c->cr_elim, n32, c->linv, c->crL, d->rhs, c->ywork,
             d->scal + 4, fs);
         KT_E(d, KT_CR_FACTOR);
     }
     // levels >= 1: the previous level's update folded into the factor launch
-    for (int l = 1; l < d->cr_nlev; l++) {
+    for (int l = 1; l < c->plan.cr_nlev; l++) {
         const int f0 = fptr[l], ne = fptr[l + 1] - f0;
         const int s0 = sptr[l], ns = sptr[l + 1] - s0;
         KT_B(d);
         k_cr32_level<<<3 * ne + ns, 256, 0, d->stream>>>(
-            d->S, d->lds, TB, d->ld, d->crf + 5 * f0, ne, d->crs + 3 * s0, n32, d->linv,
-            d->crL, d->rhs, d->ywork, d->scal + 4);
+            c->S, d->lds, TB, d->ld, c->crf + 5 * f0, ne, c->crs + 3 * s0, n32, c->linv,
+            c->crL, d->rhs, c->ywork, d->scal + 4);
         KT_E(d, KT_CR_FACTOR);
     }
     return -(int)hipGetLastError();
@@ -3527,12 +2646,13 @@ int ba_cr32_factor(ba_dev *d)
 // [2 * records] (chol_selinv_sources, the source record replaced by its tile)
 int ba_cr32_selinv(ba_dev *d, const int *src, double *sig)
 {
-    const std::vector<int> &eptr = d->plan->eptr;
+    ba_chol *c = d->chol;
+    const std::vector<int> &eptr = c->plan.eptr;
     TRY_RC(ba_ensure_dyn_lds((const void *)k_cr32_selinv, CR32_SELINV_LDS));
-    for (int l = d->cr_nlev - 1; l >= 0; l--) {
+    for (int l = c->plan.cr_nlev - 1; l >= 0; l--) {
         const int e0 = eptr[l], ne = eptr[l + 1] - e0;
         k_cr32_selinv<<<ne, 256, CR32_SELINV_LDS, d->stream>>>(
-            d->cr_elim + 3 * e0, src + 2 * e0, d->nt32, d->linv, d->crL, sig);
+            c->cr_elim + 3 * e0, src + 2 * e0, c->plan.nt32, c->linv, c->crL, sig);
     }
     return -(int)hipGetLastError();
 }
@@ -3541,10 +2661,11 @@ int ba_cr32_selinv(ba_dev *d, const int *src, double *sig)
 // it is p's, for ba_cr32_selinv: src [2 * nt32] (one record per tile)
 int ba_cr32_selinv_sources(const ba_dev *d, int *src)
 {
-    if (!d->plan || !(d->cr_nlev > 0 && d->cr32)) return -1000;
-    const std::vector<int> &elim = d->plan->elim;
+    const ba_chol *c = d->chol;
+    if (!c || !(c->plan.cr_nlev > 0 && c->plan.cr32)) return -1000;
+    const std::vector<int> &elim = c->plan.elim;
     std::vector<int> s;
-    if (chol_selinv_sources(elim, d->plan->eptr, s) || s.size() != 2 * (size_t)d->nt32)
+    if (chol_selinv_sources(elim, c->plan.eptr, s) || s.size() != 2 * (size_t)c->plan.nt32)
         return -1000;
     for (size_t i = 0; i < s.size(); i += 2) {
         src[i] = s[i] >= 0 ? elim[3 * (size_t)s[i]] : -1;
@@ -3557,34 +2678,37 @@ int ba_cr32_selinv_sources(const ba_dev *d, int *src)
 template <bool JAC>
 static void launch_cr32_fused(ba_dev *d, const cr32_fplan &P, const cr32_camupd &cu)
 {
+    ba_chol *c = d->chol;
     k_cr32_fused<JAC><<<P.b0[P.nl] + P.nrec, 256, 0, d->stream>>>(
-        d->S, d->lds, d->tb32, d->ld, d->cr_elim, d->crf, d->crs, d->nt32, d->linv, d->crL,
-        d->rhs, d->ywork, d->da, d->crflag, d->xgran, d->back_epoch, d->scal + 4, P, cu);
+        c->S, d->lds, c->plan.tb32, d->ld, c->cr_elim, c->crf, c->crs, c->plan.nt32, c->linv,
+        c->crL, d->rhs, c->ywork, d->da, c->crflag, c->xgran, c->back_epoch, d->scal + 4, P, cu);
 }
 
-int ba_chol_solve(ba_dev *d, int nospin)
+int ba_chol_solve(ba_dev *d, bool *cam_updated, int nospin)
 {
-    const int nt = d->nt;
-    d->camupd_done = 0;   // only the one-launch CR below does the camera update
+    ba_chol *c = d->chol;
+    const chol_plan &pl = c->plan;
+    const int nt = pl.nt;
+    *cam_updated = false;   // only the one-launch CR below does the camera update
     const size_t smem3 = sizeof(double) * 3 * NB * LP;
-    const std::vector<int> &eptr = d->plan->eptr, &kptr = d->plan->kptr;
+    const std::vector<int> &eptr = pl.eptr, &kptr = pl.kptr;
     TRY_RC(ba_ensure_dyn_lds((const void *)k_factor_step, smem3));
     TRY_RC(ba_ensure_dyn_lds((const void *)k_cr_factor, smem3));
     TRY_RC(ba_ensure_dyn_lds((const void *)k_cr_update, smem3));
     if (d->dense_solve == 3) {   // sequential parity solve
         KT_B(d);
-        k_chol_seq<<<1, 256, 0, d->stream>>>(d->S, d->lds, (int)d->ld, d->rhs, d->da,
+        k_chol_seq<<<1, 256, 0, d->stream>>>(c->S, d->lds, (int)d->ld, d->rhs, d->da,
                                              d->scal + 4);
         KT_E(d, KT_FACTOR);
         return -(int)hipGetLastError();
     }
-    if (d->cr_nlev > 0 && d->cr32 && d->cr_fused && d->crflag && !nospin) {   // one launch
-        const cr32_fplan &P = d->plan->fplan;
-        if (++d->back_epoch == 0) d->back_epoch = 1;
+    if (pl.cr_nlev > 0 && pl.cr32 && pl.cr_fused && c->crflag && !nospin) {   // one launch
+        const cr32_fplan &P = pl.fplan;
+        if (++c->back_epoch == 0) c->back_epoch = 1;
         cr32_camupd cu{};
         if (d->camupd_fold) {   // the next update launches no k_camera_update
             cu = cr32_camupd{d->a, d->a_new, d->rot_new, d->na, d->m};
-            d->camupd_done = 1;
+            *cam_updated = true;
         }
         KT_B(d);
         if (d->jac) launch_cr32_fused<true>(d, P, cu);
@@ -3592,102 +2716,101 @@ int ba_chol_solve(ba_dev *d, int nospin)
         KT_E(d, KT_CR_FACTOR);
         return -(int)hipGetLastError();
     }
-    if (d->cr_nlev > 0 && d->cr32) {   // camera-aligned 32-row tiles
-        const int n32 = d->nt32, TB = d->tb32;
+    if (pl.cr_nlev > 0 && pl.cr32) {   // camera-aligned 32-row tiles
+        const int n32 = pl.nt32, TB = pl.tb32;
         TRY_RC(ba_cr32_factor(d));
-        const int nrec = eptr[d->cr_nlev];
-        if (d->xgran && nrec <= 2 * d->ncu && !nospin) {   // every record co-resident: one launch
-            if (++d->back_epoch == 0) d->back_epoch = 1;
+        const int nrec = eptr[pl.cr_nlev];
+        if (c->xgran && nrec <= 2 * d->ncu && !nospin) {   // every record co-resident: one launch
+            if (++c->back_epoch == 0) c->back_epoch = 1;
             KT_B(d);
-            k_cr32_back_all<<<nrec, 256, 0, d->stream>>>(d->cr_elim, nrec, n32, TB, d->ld,
-                                                         d->linv, d->crL, d->ywork, d->da,
-                                                         d->xgran, d->back_epoch, d->scal + 4);
+            k_cr32_back_all<<<nrec, 256, 0, d->stream>>>(c->cr_elim, nrec, n32, TB, d->ld,
+                                                         c->linv, c->crL, c->ywork, d->da,
+                                                         c->xgran, c->back_epoch, d->scal + 4);
             KT_E(d, KT_CR_BACK);
             return -(int)hipGetLastError();
         }
-        for (int l = d->cr_nlev - 1; l >= 0; l--) {
+        for (int l = pl.cr_nlev - 1; l >= 0; l--) {
             const int e0 = eptr[l], ne = eptr[l + 1] - e0;
             KT_B(d);
-            k_cr32_back<<<ne, 256, 0, d->stream>>>(d->cr_elim + 3 * e0, n32, TB, d->ld,
-                                                   d->linv, d->crL, d->ywork, d->da);
+            k_cr32_back<<<ne, 256, 0, d->stream>>>(c->cr_elim + 3 * e0, n32, TB, d->ld,
+                                                   c->linv, c->crL, c->ywork, d->da);
             KT_E(d, KT_CR_BACK);
         }
         return -(int)hipGetLastError();
     }
-    if (d->cr_nlev > 0) {   // (status cleared by k_assemble_tiles)
+    if (pl.cr_nlev > 0) {   // (status cleared by k_assemble_tiles)
         // one workgroup per CU (LDS): fan a level out over 5 (factor) / 4
         // (update) workgroups per tile while that still fits in one wave of
         // workgroups -- the levels are latency bound, the chip mostly idle
         const int ncu = d->ncu;
-        for (int l = 0; l < d->cr_nlev; l++) {
+        for (int l = 0; l < pl.cr_nlev; l++) {
             const int e0 = eptr[l], ne = eptr[l + 1] - e0;
             const int k0 = kptr[l], nk = kptr[l + 1] - k0;
             const int fs = 5 * ne <= ncu, us = 4 * nk <= ncu;
             KT_B(d);
             k_cr_factor<<<fs ? 5 * ne : ne, 256, smem3, d->stream>>>(
-                d->S, d->lds, d->cr_elim + 3 * e0, nt, d->linv, d->crL, d->rhs, d->ywork,
+                c->S, d->lds, c->cr_elim + 3 * e0, nt, c->linv, c->crL, d->rhs, c->ywork,
                 d->scal + 4, fs);
             KT_E(d, KT_CR_FACTOR);
             if (nk > 0) {
                 KT_B(d);
                 k_cr_update<<<us ? 4 * nk : nk, 256, smem3, d->stream>>>(
-                    d->S, d->lds, d->cr_keep + 4 * k0, nt, d->crL, d->rhs, d->ywork, us);
+                    c->S, d->lds, c->cr_keep + 4 * k0, nt, c->crL, d->rhs, c->ywork, us);
                 KT_E(d, KT_CR_UPDATE);
             }
         }
-        for (int l = d->cr_nlev - 1; l >= 0; l--) {
+        for (int l = pl.cr_nlev - 1; l >= 0; l--) {
             const int e0 = eptr[l], ne = eptr[l + 1] - e0;
             KT_B(d);
-            k_cr_back<<<ne, 256, 0, d->stream>>>(d->cr_elim + 3 * e0, nt, d->linv, d->crL,
-                                                 d->ywork, d->da);
+            k_cr_back<<<ne, 256, 0, d->stream>>>(c->cr_elim + 3 * e0, nt, c->linv, c->crL,
+                                                 c->ywork, d->da);
             KT_E(d, KT_CR_BACK);
         }
         return -(int)hipGetLastError();
     }
     // the envelope factor's in-launch hand-off (not in a re-solve)
-    unsigned *kflag = nospin ? nullptr : d->kflag;
-    if (kflag && ++d->fac_epoch == 0) d->fac_epoch = 1;
-    if (d->nd_np > 0) {   // nested dissection: the arcs side by side, then the separator
-        const int np = d->nd_np, s0 = d->nd_a0[np];
-        const long long L = d->slds;
+    unsigned *kflag = nospin ? nullptr : c->kflag;
+    if (kflag && ++c->fac_epoch == 0) c->fac_epoch = 1;
+    if (pl.nd_np > 0) {   // nested dissection: the arcs side by side, then the separator
+        const int np = pl.nd_np, s0 = pl.nd_a0[np];
+        const long long L = pl.slds;
         TRY_RC(ba_ensure_dyn_lds((const void *)k_factor_multi, smem3));
         int nsteps = 0;
-        for (int t = 0; t < np; t++) nsteps = std::max(nsteps, d->nd_a0[t + 1] - d->nd_a0[t]);
+        for (int t = 0; t < np; t++) nsteps = std::max(nsteps, pl.nd_a0[t + 1] - pl.nd_a0[t]);
         bool run = env_run_on(d, kflag, nsteps);
         if (run) {
             env_runs Rn{};
             Rn.np = np;
             for (int t = 0; t < np; t++) {
-                Rn.k0[t] = d->nd_a0[t];
-                Rn.k1[t] = d->nd_a0[t + 1];
+                Rn.k0[t] = pl.nd_a0[t];
+                Rn.k1[t] = pl.nd_a0[t + 1];
             }
-            if (env_runner_start(d, Rn, L, d->nd_rhs)) run = false;   // the launches alone
+            if (env_runner_start(d, Rn, L, c->nd_rhs)) run = false;   // the launches alone
         }
         for (int st = 0; st < nsteps; st++) {
             nd_step P;
-            chol_nd_step(*d->plan, st, run, &P);
+            chol_nd_step(pl, st, run, &P);
             const int nbk = P.b0[P.np];
             KT_B(d);
             k_factor_multi<<<nbk, 256, kflag ? sizeof(double) * 2 * NB * LP : smem3, d->stream>>>(
-                d->S, L, d->pan_list, P, s0, d->linv,
-                                                          d->nd_rhs, d->ywork, d->scal + 4, kflag,
-                                                          d->fac_epoch, env_rm_of(d, 0));
+                c->S, L, c->pan_list, P, s0, c->linv, c->nd_rhs, c->ywork, d->scal + 4, kflag,
+                c->fac_epoch, env_rm_of(d, 0));
             KT_E(d, KT_FACTOR);
         }
         if (run) VLGBA_CHECK(hipStreamWaitEvent(d->stream, d->ev_join, 0));
-        if (d->nd_nrec > 0) {
+        if (pl.nd_nrec > 0) {
             const size_t smem2 = sizeof(double) * 2 * NB * LP;
             TRY_RC(ba_ensure_dyn_lds((const void *)k_sep_update, smem2));
             KT_B(d);
-            k_sep_update<<<d->nd_nrec, 256, smem2, d->stream>>>(
-                d->S, L, d->nd_pair, d->nd_rec, d->nd_klist, d->ywork, d->nd_part);
-            k_sep_reduce<<<d->nd_npair, 256, 0, d->stream>>>(d->S, L, d->nd_pair, d->nd_pptr,
-                                                             d->nd_part, d->nd_rhs);
+            k_sep_update<<<pl.nd_nrec, 256, smem2, d->stream>>>(
+                c->S, L, c->nd_pair, c->nd_rec, c->nd_klist, c->ywork, c->nd_part);
+            k_sep_reduce<<<pl.nd_npair, 256, 0, d->stream>>>(c->S, L, c->nd_pair, c->nd_pptr,
+                                                             c->nd_part, c->nd_rhs);
             KT_E(d, KT_SYRK);
         }
-        TRY_RC(envelope_columns(d, s0, nt, L, d->nd_rhs, kflag));
-        TRY_RC(envelope_backward(d, L, d->nd_x, nospin));
-        k_nd_scatter<<<(int)((d->lds + 255) / 256), 256, 0, d->stream>>>(d->nd_prow, d->nd_x,
+        TRY_RC(envelope_columns(d, s0, nt, L, c->nd_rhs, kflag));
+        TRY_RC(envelope_backward(d, L, c->nd_x, nospin));
+        k_nd_scatter<<<(int)((d->lds + 255) / 256), 256, 0, d->stream>>>(c->nd_prow, c->nd_x,
                                                                          d->da, d->lds);
         return -(int)hipGetLastError();
     }

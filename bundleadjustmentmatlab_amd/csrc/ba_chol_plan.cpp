@@ -277,7 +277,7 @@ int chol_plan_build(const chol_plan_in &in, chol_plan &out)
         std::vector<int> &elim = out.elim, &keep = out.keep, &eptr = out.eptr, &kptr = out.kptr;
         cr_records(nt, elim, keep, eptr, kptr);
         out.cr_nlev = (int)eptr.size() - 1;
-        {   // the CR's algorithmic flops (ba_dev::fl_factor): per elimination
+        {   // the CR's algorithmic flops (chol_plan::fl_factor): per elimination
             // record (e, p, q) the factor + inverse of D_e, y_e and one panel per
             // neighbour; per kept record (k, e-, e+, k2) the update of D_k and r_k
             // by its eliminated neighbours and the fill towards k2; the back
@@ -491,7 +491,7 @@ int chol_plan_build(const chol_plan_in &in, chol_plan &out)
         out.nd_npair = (int)pairs.size() / 2;
         out.nd_nrec = (int)rec.size() / 3;
     }
-    {   // the envelope's algorithmic flops (see ba_dev::fl_factor; the CR's: above)
+    {   // the envelope's algorithmic flops (see chol_plan::fl_factor; the CR's: above)
         const double t = NB;
         const double potri = 2.0 * t * t * t / 3.0, gemm = 2.0 * t * t * t, gemv = 2.0 * t * t;
         for (int k = 0; k < nt && !out.cr_nlev && in.dense_solve != 3; k++) {
@@ -550,17 +550,10 @@ void chol_nd_step(const chol_plan &plan, int st, bool run, nd_step *Pout)
         P.pb[u + 1] = P.pb[u] + T;
         nbk += 1 + T;
     }
-    // the trailing workgroups: each arc's share of the cap (with the hand-off)
-    int ttot = 0;
-    for (int u = 0; u < P.np; u++) ttot += P.ntr[u];
-    const int tw = ttot;   // one workgroup per trailing pair
+    // the trailing workgroups: one per trailing pair
     for (int u = 0; u < P.np; u++) {
-        const int nw = tw == ttot ? P.ntr[u]
-                                  : (P.ntr[u] == 0 ? 0
-                                                   : std::max(1, (int)((long long)tw *
-                                                                       P.ntr[u] / ttot)));
-        P.ts[u] = nw;
-        P.tb[u + 1] = P.tb[u] + nw;
+        P.ts[u] = P.ntr[u];
+        P.tb[u + 1] = P.tb[u] + P.ts[u];
     }
     if (!P.grouped) {   // arc-major: arc u's trailing workgroups follow its panels
         int acc = 0;

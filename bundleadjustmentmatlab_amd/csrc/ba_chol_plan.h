@@ -93,7 +93,13 @@ struct chol_plan {
     std::vector<int> crow, prow, rowsrc;       // [m], [lds], [slds]
     std::vector<int> pairs, pptr, rec, klist;  // separator pairs and their arc-column chunks
     int nd_npair = 0, nd_nrec = 0;
-    // algorithmic flops of one solve (ba_dev::fl_factor)
+    // algorithmic flops of one solve (bench.py's roofline of the solve kernels):
+    // tile-dense potrf + trtri of the diagonal tiles, panel / trailing / fill /
+    // SYRK GEMMs and the triangular GEMVs, each counted once (the redundant
+    // factorisations of the role-split records are not).  fl_factor: the
+    // launches timed as k_factor_step / k_cr_factor (with the one-launch CR its
+    // back substitution too); fl_syrk: k_sep_update / k_sep_reduce; fl_back:
+    // k_backward(_all) / the per-level CR back launches
     double fl_factor = 0.0, fl_syrk = 0.0, fl_back = 0.0;
     // what the setup allocates besides the lists
     bool back_one_launch = false;   // every column co-resident: pan_ptr + xgran64

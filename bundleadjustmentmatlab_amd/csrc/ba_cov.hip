@@ -47,6 +47,7 @@
 // values are the same, hence so are the results, bit for bit.  cfg3 (tracks of
 // 6, 10.5 M pairs): 394 us packed, 400 us dense (profiles/cov_time_cfg3.txt).
 #include "ba_internal.h"
+#include "ba_chol.h"
 
 // One lane's pairs of one point: the six lower entries of its part of T_i.  Wp:
 // the point's W rows (LDS or global memory: a call site of its own for each, so
@@ -323,7 +324,8 @@ int ba_cov_extract(ba_dev *d, const double *sig, const unsigned char *fixed, con
     const long long q = (long long)d->na * d->na * ((long long)nb + d->m);
     if (q > 0)
         k_cov_extract<<<(int)((q + 255) / 256), 256, 0, d->stream>>>(
-            sig, d->nt32, d->tb32, d->na, d->m, fixed, bj, bk, nb, diag, packed);
+            sig, d->chol->plan.nt32, d->chol->plan.tb32, d->na, d->m, fixed, bj, bk, nb, diag,
+            packed);
     return -(int)hipGetLastError();
 }
 

@@ -28,7 +28,7 @@
 // BA_CR_MAXLEV): shared with the host planners
 #include "ba_limits.h"
 
-struct chol_plan;   // the reduced solve's host plan (ba_chol_plan.h)
+struct ba_chol;   // the reduced solve's state (ba_chol.h)
 
 #define VLGBA_CHECK(x)                                                              \
     do {                                                                            \
@@ -112,111 +112,37 @@ struct ba_dev {
     int nb;            // blocks
     long long T;       // terms
     int *blk_jk, *blk_ptr, *term;
-    double *sblk, *rhs, *S, *da;
+    double *sblk, *rhs, *da;
     long long ld;      // NA*m
     long long lds;     // ld rounded up to the Cholesky tile (padding rows = identity)
-    double *linv;      // [lds/64][64*64] inverses of the diagonal Cholesky tiles
-    double *ywork;     // [lds] forward-solve result
-    // tile envelope of the reduced system (64 x 64 tiles): tile row i of L is
-    // non-zero only in tile columns >= tfirst[i] (profile is preserved by the
-    // factorisation), so tiles left of it are never touched.
-    // The host plan of the solve (chol_plan_build, ba_chol_plan.cpp: tfirst, the
-    // panel lists, the CR records' level pointers, the launch plans) is *plan,
-    // owned by ba_chol_setup / ba_chol_free; the scalars other files read are
-    // mirrored in the fields below.
-    chol_plan *plan;
-    int nt;
-    int *pan_list;     // device: tile rows i > k with tfirst[i] <= k, per k
-    int *pan_ptr;      // device [nt+1] offsets into pan_list (k_backward_all)
-    unsigned long long *xgran64;  // [nt][128] x_k granules of the one-launch backward
-    unsigned *kflag;   // [nt] envelope factor: L_kk^-1 / y_k published (epoch fac_epoch)
-    unsigned fac_epoch;
-    unsigned *rflag;    // [4 nt + 1] runner mode's flags + its timeout word (k_env_runner;
-                        // opt-in: VLGBA_ENV_RUNNER=1)
-    int env_runner;
-    int runner_runs;          // runner launches made (vlgba_plan_info [28])
-    int debug_runner_fail;    // the next starts fail (vlgba_debug_force_status word 6)
-    hipStream_t rstream;   // the runner's stream (highest priority)
-    int *env_tiles;    // device [n_env][2] (i, k) tiles inside the envelope
-    int *tb_ptr, *tb_blk;  // device: per envelope tile, the co-visible blocks overlapping it
-    int n_env;
+    // the reduced solve (ba_chol.h): its plan, the dense S and its factors, the
+    // lists and flags of the method the plan chose.  Owned by ba_chol_setup /
+    // ba_chol_free; null in stage-mode contexts (which solve nothing)
+    ba_chol *chol;
     int dense_solve;   // 0 auto, 1: every lower tile (measurement), 2: envelope, no CR,
                        // 3: sequential Cholesky (parity mode), 4: nested dissection
                        // whenever the cameras split (tests; 0 takes it when it pays)
-    // block cyclic reduction (tile-tridiagonal S): per level, eliminated tiles
-    // (e, p, q) and kept tiles (k, e-, e+, k2); -1 = none
-    int cr_nlev;
-    int *cr_elim, *cr_keep;       // device [3 * ne], [4 * nk]
-    double *crL;                  // [2][nt][64*64] L(p, e) | L(q, e)
-    // camera-aligned cyclic reduction: tiles of tb32 = NA * floor(32 / NA)
-    // rows (whole cameras, <= 32), padded to 32 in LDS with an identity block;
-    // chosen when S is tridiagonal at that granularity (half the pivot chain
-    // per level of the 64-row tiles).  crL then holds [2][nt32][32*32] and
-    // linv [nt32][32*32].
-    int cr32, tb32, nt32;
-    // fused levels (L >= 1): records (e, p, q, em, ep) and survivors (k, em, ep)
-    int *crf, *crs;               // device
-    // one-launch back substitution (k_cr32_back_all): x of every tile as
-    // 64 epoch-tagged 8-byte granules, read by the tiles of the level below
-    unsigned long long *xgran;    // [nt32][64]
-    unsigned back_epoch;          // per solve, never 0
-    // the whole CR in one launch (k_cr32_fused): epoch flags per (level, tile,
-    // role 0..2 | survivor); cr_fused = 0 (VLGBA_CR_FUSED=0) keeps the
-    // per-level launches
-    unsigned *crflag;             // [nlev][nt32][5]
-    int cr_fused;
+    // the two decisions a pass takes from the plan (ctx_setup):
     // direct assembly (camera-aligned CR, one rank, fast path): k_schur_reduce
     // writes each block's lower entries straight into S (and the pinv rule
     // of exactly-zero diagonals), so no k_assemble_tiles launch.  Needs every
-    // lower entry of every diagonal CR tile covered by a block (asm_direct_ok,
-    // chol_plan_build): the CR writes only those tiles, so S's other entries
+    // lower entry of every diagonal CR tile covered by a block (the plan's
+    // asm_direct_ok): the CR writes only those tiles, so S's other entries
     // keep the zeros of the setup.
-    int asm_direct_ok, asm_direct;
+    int asm_direct;
     // camera update inside the one-launch CR (k_cr32_fused, x = da in camera
     // order, a tile = whole cameras): each back record forms a_new = a + da
     // and the rotation table of its own cameras from x_e in LDS, and the
     // update's final sums (k_sum_parts3) form the camera part of dp'(lambda dp
-    // + g) -- so the update that directly follows such a solve launches no
-    // k_camera_update.  camupd_fold: allowed (setup; VLGBA_CAMUPD_FOLD=0: off);
-    // camupd_done: set by the solve that did it, consumed by the next
-    // ba_launch_update (every other solve and every other writer of da clears
-    // it: their update launches k_camera_update).
-    int camupd_fold, camupd_done;
-    // one-level nested dissection of the envelope (chol_plan_build, auto mode
-    // when S is not tridiagonal; dense_solve 4 forces it): the cameras split
-    // into nd_np arcs of consecutive cameras minus the separator (cameras
-    // coupled to an earlier arc).  Rows: arc 0 | arc 1 | ... | separator, each
-    // part padded to whole 64-row tiles.  Arcs never couple to each other, so
-    // step s factors column s of every arc in ONE launch (k_factor_multi);
-    // the arcs' contribution to the separator block is one SYRK
-    // (k_sep_update / k_sep_reduce), then the separator's columns.
-    int nd_np;                    // arcs (0: natural order)
-    int nd_grouped;               // k_factor_multi's workgroups grouped by role (nd_step)
-    int nd_a0[BA_ND_MAX + 1];     // first tile of arc t; nd_a0[nd_np] = first separator tile
-    long long slds;               // rows of the reordered system (nt * 64)
-    int *nd_crow;                 // device [m] first row of camera j
-    int *nd_prow;                 // device [lds] row of camera-space entry c (-1: padding)
-    int *nd_rowsrc;               // device [slds] camera-space entry of row r (-1: padding)
-    double *nd_rhs, *nd_x;        // [slds] the rhs / solution in row order
-    int nd_npair, nd_nrec;        // separator tile pairs, (pair, arc-column chunk) records
-    int *nd_pair;                 // device [npair][2] (i, j), i >= j, ascending
-    int *nd_pptr;                 // device [npair + 1] records of each pair
-    int *nd_rec;                  // device [nrec][3] (pair, kofs, kcnt)
-    int *nd_klist;                // device: the arc columns of the records
-    double *nd_part;              // [nrec][64*64 + 64] per-record L_i L_j^T | L_i y
-    // algorithmic flops of one reduced solve (chol_plan_build; bench.py's roofline
-    // of the solve kernels): tile-dense potrf + trtri of the diagonal tiles,
-    // panel / trailing / fill / SYRK GEMMs and the triangular GEMVs, each counted
-    // once (the redundant factorisations of the role-split records are not).
-    // fl_factor: the launches timed as k_factor_step / k_cr_factor (with the
-    // one-launch CR its back substitution too); fl_syrk: k_sep_update /
-    // k_sep_reduce; fl_back: k_backward(_all) / the per-level CR back launches
-    double fl_factor, fl_syrk, fl_back;
+    // + g).  camupd_fold: allowed (setup; VLGBA_CAMUPD_FOLD=0: off).  A solve
+    // that did it says so (ba_chol_solve's cam_updated), and the pass hands
+    // that to its update (ba_launch_update), which then launches no
+    // k_camera_update.
+    int camupd_fold;
     // reductions: partial sums per block of the reducing kernels, in fixed order
     double *part;      // [3][PART_MAX]
     double *scal;      // [8] : 0 old_sse, 1 new_sse, 2 dpg cams, 3 dpg pts, 4 non-positive
                        // pivot, 5 hand-off spin timeout (the solve's status words)
-    int *chol_cnt;     // arrival counters for the triangular solves
     // ---- fast (chunked) Schur path: points in chunks of <= CH_OBS observations;
     // per chunk the co-visible blocks it touches ("slots") and the cameras it
     // sees ("e-slots") get one partial each, reduced per block in chunk order.
@@ -306,11 +232,9 @@ struct ba_dev {
     double *xh_out;    // [N][2] projections (stage 1 and stage 3)
     double *B_out;     // [N][6] point Jacobians (stage 1)
     unsigned char *obs_vis;  // [N] stage 3: 0 = structural-only pair (no projection)
-    double red_lambda; // ... at this lambda
     int schur_owner;   // this rank adds U* / eA into the reduced system (every rank
                        // adds its own partials)
     int dpg_lambda;    // this rank adds the lambda dp'dp part of the camera dpg
-    double scal_host[8];
     struct ba_ktimer *kt;   // NULL unless kernel timing is enabled
     hipStream_t stream;
     // second stream: the camera reduction runs there, concurrently with V*^-1
@@ -345,7 +269,9 @@ int ba_launch_camera_reduce(ba_dev *d, ba_flags f, int fuse = 0);
 int ba_launch_damp_point(ba_dev *d, double lambda);
 int ba_launch_schur(ba_dev *d, double lambda);
 int ba_launch_assemble(ba_dev *d);
-int ba_launch_update(ba_dev *d, double lambda, ba_flags f);
+// cam_updated: the solve directly before formed a_new / rot_new itself
+// (ba_chol_solve), so no k_camera_update; false after every other writer of da
+int ba_launch_update(ba_dev *d, double lambda, ba_flags f, bool cam_updated);
 int ba_launch_yeb(ba_dev *d);
 // per observation (internal order) at the current parameters: e [N][2] = x - x_hat
 // (unweighted), w [N], rho [N] of the context's loss; any pointer may be NULL
@@ -368,6 +294,9 @@ int ba_launch_assemble_plain(ba_dev *d, double *S, long long ld, int lower_only)
 int ba_launch_parity_old_sse(ba_dev *d);
 int ba_launch_parity_new_sums(ba_dev *d, double lambda);
 // ---- ba_chol.hip ----
+// Everything below but ba_chol_free, ba_fix_diag_plain, ba_pinv_apply and
+// ba_cr32_selinv_sources needs a solving context: d->chol set by ba_chol_setup
+// (it is null in stage-mode contexts and after ba_chol_free).
 int ba_chol_setup(ba_dev *d, const int *blk_jk_host, int nb);
 void ba_chol_free(ba_dev *d);
 int ba_chol_prepare(ba_dev *d);
@@ -375,10 +304,12 @@ int ba_assemble_tiles(ba_dev *d);   // envelope tiles of S + pinv rule + status,
 int ba_fix_diag_plain(ba_dev *d, double *S, long long ld);
 int ba_chol_fix_diag(ba_dev *d);
 // nospin = 1: only launches that never wait on other workgroups (the
-// per-level / per-column paths) -- the re-solve after a hand-off timeout
-int ba_chol_solve(ba_dev *d, int nospin = 0);
+// per-level / per-column paths) -- the re-solve after a hand-off timeout.
+// *cam_updated = true when the solve also formed a_new / rot_new (the one-launch
+// CR with camupd_fold), else false
+int ba_chol_solve(ba_dev *d, bool *cam_updated, int nospin = 0);
 // camera-aligned CR (cr32) only: the factor launches of the per-level path
-// alone (no back substitution, da and camupd_done untouched); the selected
+// alone (no back substitution, da untouched); the selected
 // inverse's tile sources on the host (src [2 * nt32]: tile holding Sigma_qp or
 // -1, 1 when it is p's) and its descent on the device (src uploaded, sig
 // [3][nt32][32 * 32]: Sigma_ee | Sigma_ep | Sigma_eq, row major)

@@ -28,6 +28,7 @@
 // the oracle's (and the reference's, modulo libm).  Only the scalar cost sums
 // use tree reductions (MATLAB's BLAS dot order is unknowable anyway).
 #include "ba_internal.h"
+#include "ba_chol.h"
 #include "ba_camera.h"
 #include "vlg_math.h"
 #include "../../include/vlgba.h"
@@ -2670,7 +2671,7 @@ struct ba_sum3 {
     double *hres;
     double seq;
     unsigned *cnt;   // zero between launches (the last block resets it)
-    // optional (the camera update ran inside the solve, ba_dev::camupd_done):
+    // optional (the camera update ran inside the solve, ba_launch_update's cam_updated):
     // block 2 first forms its own partials part[2][0 .. n[2]) -- the camera
     // part of dp'(lambda dp + g), one per 64 cameras: k_camera_update's
     // per-lane expression and wave tree
@@ -2963,7 +2964,7 @@ static int launch_schur_fast(ba_dev *d, double lambda)
         lg.L0 = d->long_o0_h;
     }
     ba_direct dir{nullptr, 0, nullptr};
-    if (d->asm_direct) dir = ba_direct{d->S, d->lds, d->scal + 4};
+    if (d->asm_direct) dir = ba_direct{d->chol->S, d->lds, d->scal + 4};
     const size_t lsh = lg.pair_ptr ? sizeof(double) * 2 * BA_LMATCH_BATCH * 3 * NA : 0;
     k_schur_reduce<NA><<<d->nb, bs, lsh, d->stream>>>(
         d->blk_jk, d->blk_gptr, d->blk_gslots, d->cam_gptr, d->cam_gslots, d->spart, d->epart,
@@ -3034,7 +3035,7 @@ int ba_launch_assemble(ba_dev *d)
 // ---- the update (ba_launch_update) and the steps its branches share ----
 // The camera update: k_camera_update, or its analytic-Jacobian twin
 // (ba_dev::jac) -- unless folded: a_new and rot_new are then the solve's
-// (ba_dev::camupd_done)
+// (ba_launch_update's cam_updated)
 static int launch_camera_update(ba_dev *d, int gc, double lam_dpg, bool folded)
 {
     if (folded) return 0;
@@ -3103,14 +3104,13 @@ static int launch_final_sums(ba_dev *d, const double *sse_part, const double *dp
 // pass's own linearisation (App. A Q12).  Chunked (VLGBA_FUSED=0): the same
 // with k_point_update_chunk for the one pass and no linearisation.  Else the
 // per-point update and its three sums.
-int ba_launch_update(ba_dev *d, double lambda, ba_flags f)
+int ba_launch_update(ba_dev *d, double lambda, ba_flags f, bool cam_updated)
 {
-    // the camera update of the one-launch CR that ran directly before
-    // (ba_dev::camupd_done; consumed here), on the paths whose final sums are
-    // k_sum_parts3 -- every other update launches k_camera_update
+    // cam_updated: the one-launch CR that ran directly before did the camera
+    // update (ba_chol_solve), on the paths whose final sums are k_sum_parts3 --
+    // every other update launches k_camera_update
     const bool chunked = !d->ordered && d->nch > 0 && !d->obs_vis && !d->xh_out;
-    const bool folded = d->camupd_done && (d->fused || chunked);
-    d->camupd_done = 0;
+    const bool folded = cam_updated && (d->fused || chunked);
     const int gc = (d->m + 63) / 64;
     // lambda dp'dp once over the ranks (each adds da' eA of its partial eA)
     const double lam_dpg = d->dpg_lambda ? lambda : 0.0;

@@ -15,7 +15,7 @@
 // dense solve, and a 3-scalar all-reduce drives the accept/reject decision.
 #include "ba_internal.h"
 #include "ba_plan.h"   // the host planner: sort_obs, order_points_by_kind, plan_host
-#include "ba_chol_plan.h"   // the reduced solve's plan (ba_dev::plan)
+#include "ba_chol.h"   // the reduced solve's state and plan (ba_dev::chol)
 #include "../../include/vlgba.h"
 
 #include <rccl/rccl.h>
@@ -743,18 +743,19 @@ static int ctx_setup(vlgba_ctx *c, const vlgba_problem *p, const host_obs &h,
         // between the block sums and the solve, the fast path's block sums, no
         // long tracks (k_schur_long_acc adds to the sums after them);
         // VLGBA_ASM_DIRECT=0 keeps k_assemble_tiles (A/B)
+        const chol_plan &P = d.chol->plan;
         const char *ad = std::getenv("VLGBA_ASM_DIRECT");
-        d.asm_direct = d.asm_direct_ok && !(ad && ad[0] == '0') && fast && !d.ordered &&
-                       c->world == 1 && !c->comm && d.nl == 0 && d.cr_nlev > 0 && d.cr32 &&
-                       d.nd_np == 0;
+        d.asm_direct = P.asm_direct_ok && !(ad && ad[0] == '0') && fast && !d.ordered &&
+                       c->world == 1 && !c->comm && d.nl == 0 && P.cr_nlev > 0 && P.cr32 &&
+                       P.nd_np == 0;
         // camera update inside the one-launch CR (ba_dev::camupd_fold): x = da
         // in camera order, every tile a whole number of cameras, the Euclidean
         // models' rotation table, the fast path's final sums (k_sum_parts3);
         // VLGBA_CAMUPD_FOLD=0 keeps k_camera_update (A/B, tests)
         const char *cf = std::getenv("VLGBA_CAMUPD_FOLD");
         d.camupd_fold = !(cf && cf[0] == '0') && fast && !d.ordered && d.nch > 0 &&
-                        d.cr_nlev > 0 && d.cr32 && d.cr_fused && d.crflag && d.nd_np == 0 &&
-                        na != BA_PROJ_NA && na <= 10 && d.tb32 % na == 0 &&
+                        P.cr_nlev > 0 && P.cr32 && P.cr_fused && d.chol->crflag && P.nd_np == 0 &&
+                        na != BA_PROJ_NA && na <= 10 && P.tb32 % na == 0 &&
                         d.ld == (long long)na * p->m;
     } else {
         TRY(ctx_alloc(c, &d.da, (size_t)d.lds));
@@ -1062,6 +1063,19 @@ static int collect_scalars(vlgba_ctx *c, bool spin, double hs[6])
     return 0;
 }
 
+// The end the recovery paths share: the update with the da they formed (never
+// the one-launch CR's, so k_camera_update runs; nothing publishes), the parity
+// sums, the scalars
+static int recovery_update(vlgba_ctx *c, double lam, double hs[6])
+{
+    ba_dev &d = c->d;
+    d.publish_req = 0;
+    d.published = 0;
+    TRY(ba_launch_update(&d, lam, c->flags, false));
+    if (d.parity) TRY(ba_launch_parity_new_sums(&d, lam));
+    return collect_scalars(c, false, hs);
+}
+
 // A hand-off spin of the one-launch solve gave up (timeout word scal[5]):
 // nothing is wrong with S, the launch just did not finish in time.  Re-form
 // S and e_ (the solve works in place), solve with the launches that never
@@ -1073,12 +1087,9 @@ static int resolve_nospin(vlgba_ctx *c, double lam, double hs[6])
     ba_dev &d = c->d;
     TRY(schur_phase(c, lam));
     TRY(ba_launch_assemble(&d));
-    TRY(ba_chol_solve(&d, 1));
-    d.publish_req = 0;
-    d.published = 0;
-    TRY(ba_launch_update(&d, lam, c->flags));
-    if (d.parity) TRY(ba_launch_parity_new_sums(&d, lam));
-    TRY(collect_scalars(c, false, hs));
+    bool cam_updated = false;   // (never set by a solve without spins)
+    TRY(ba_chol_solve(&d, &cam_updated, 1));
+    TRY(recovery_update(c, lam, hs));
     c->spin_retries++;
     // one of the envelope runner's own hand-offs gave up (most likely its side
     // stream sharing a hardware queue with the library stream, so the column
@@ -1200,14 +1211,9 @@ static int nd_natural_retry(vlgba_ctx *c, double lam, double hs[6])
                       c->pinv_e, (rocblas_int)ld) != rocblas_status_success)
             return VLGBA_E_ARG;
     }
-    d.camupd_done = 0;   // (da is not the one-launch CR's)
     VLGBA_CHECK(hipMemcpyAsync(d.da, c->pinv_e, sizeof(double) * ld, hipMemcpyDeviceToDevice,
                                d.stream));
-    d.publish_req = 0;
-    d.published = 0;
-    TRY(ba_launch_update(&d, lam, c->flags));
-    if (d.parity) TRY(ba_launch_parity_new_sums(&d, lam));
-    TRY(collect_scalars(c, false, hs));
+    TRY(recovery_update(c, lam, hs));
     c->nd_retries++;
     if (c->rank == 0 && !std::getenv("VLGBA_QUIET"))
         std::fprintf(stderr, "[vlgba] non-positive pivot in the nested-dissection order: the "
@@ -1243,12 +1249,7 @@ static int pinv_fallback(vlgba_ctx *c, double lam, double hs[6])
         if (info != 0) return VLGBA_E_ARG;   // the eigensolver did not converge
     }
     TRY(ba_pinv_apply(&d, c->pinv_S, c->pinv_ev, ld, d.rhs, c->pinv_w, d.da));
-    d.camupd_done = 0;   // (da is not the one-launch CR's)
-    d.publish_req = 0;
-    d.published = 0;
-    TRY(ba_launch_update(&d, lam, c->flags));
-    if (d.parity) TRY(ba_launch_parity_new_sums(&d, lam));
-    TRY(collect_scalars(c, false, hs));
+    TRY(recovery_update(c, lam, hs));
     c->pinv_used++;
     if (c->rank == 0 && !std::getenv("VLGBA_QUIET"))
         std::fprintf(stderr,
@@ -1309,7 +1310,8 @@ static int lm_pass(vlgba_ctx *c, int relinearize, vlgba_step_info *info)
     mark(c, 4);
     TRY(ba_launch_assemble(&d));
     mark(c, 5);
-    TRY(ba_chol_solve(&d));
+    bool cam_updated = false;   // the solve formed a_new / rot_new (one-launch CR)
+    TRY(ba_chol_solve(&d, &cam_updated));
     for (int w = 4; w <= 5; w++) {   // test hooks: as if a pivot failed / a spin gave up
         int &k = w == 4 ? c->debug_pivots : c->debug_timeouts;
         if (k > 0) {
@@ -1325,7 +1327,7 @@ static int lm_pass(vlgba_ctx *c, int relinearize, vlgba_step_info *info)
     const bool spin = (c->world == 1 || c->comm) && !c->timing;
     d.publish_req = spin && !c->comm;   // the fast update's final-sums launch publishes
     d.published = 0;
-    TRY(ba_launch_update(&d, lam, c->flags));
+    TRY(ba_launch_update(&d, lam, c->flags, cam_updated));
     d.publish_req = 0;
     if (d.parity) TRY(ba_launch_parity_new_sums(&d, lam));
     mark(c, 7);
@@ -1340,7 +1342,7 @@ static int lm_pass(vlgba_ctx *c, int relinearize, vlgba_step_info *info)
         TRY(resolve_nospin(c, lam, hs));
         info->spin_retry = 1;
     }
-    if (hs[4] != 0.0 && d.nd_np > 0) {   // the nested-dissection order's pivot: the
+    if (hs[4] != 0.0 && d.chol->plan.nd_np > 0) {   // the nested-dissection order's pivot: the
         const int rc = nd_natural_retry(c, lam, hs);   // natural order first
         if (rc < 0) return rc;
         info->nd_retry = 1;
@@ -1370,10 +1372,11 @@ static int lm_pass(vlgba_ctx *c, int relinearize, vlgba_step_info *info)
             // the solve's algorithmic flops (chol_plan_build's count) on the timers
             // that ran them: one-launch / per-level CR, or the envelope's steps,
             // separator SYRK and backward solve
-            const bool cr = d.cr_nlev > 0;
-            kt->flops[cr ? KT_CR_FACTOR : KT_FACTOR] += d.fl_factor;
-            kt->flops[KT_SYRK] += d.fl_syrk;
-            kt->flops[cr ? KT_CR_BACK : KT_BACKWARD] += d.fl_back;
+            const chol_plan &P = d.chol->plan;
+            const bool cr = P.cr_nlev > 0;
+            kt->flops[cr ? KT_CR_FACTOR : KT_FACTOR] += P.fl_factor;
+            kt->flops[KT_SYRK] += P.fl_syrk;
+            kt->flops[cr ? KT_CR_BACK : KT_BACKWARD] += P.fl_back;
         }
     }
     info->old_sse = hs[0];
@@ -1770,12 +1773,13 @@ static int cov_setup_selected(vlgba_ctx *c)
 {
     ba_dev &d = c->d;
     if (c->cov_sig) return 0;
-    std::vector<int> src(2 * (size_t)d.nt32);
+    const int nt32 = d.chol->plan.nt32;   // (the selected method: a solving context)
+    std::vector<int> src(2 * (size_t)nt32);
     TRY(ba_cr32_selinv_sources(&d, src.data()));
     TRY(ctx_alloc(c, &c->cov_selsrc, src.size()));
     TRY(upload(c->cov_selsrc, src.data(), src.size(), d.stream));
     VLGBA_CHECK(hipStreamSynchronize(d.stream));   // src goes out of scope
-    const size_t cnt = (size_t)3 * 32 * 32 * d.nt32;
+    const size_t cnt = (size_t)3 * 32 * 32 * nt32;
     double *sig = nullptr;
     TRY(ctx_alloc(c, &sig, cnt));
     VLGBA_CHECK(hipMemsetAsync(sig, 0, sizeof(double) * cnt, d.stream));
@@ -1907,7 +1911,7 @@ static int cov_run(vlgba_ctx *c, int scale, double *cov_a, double *cov_a_full, d
                        ((double)(ld - nfixed) + (c->flags.fix_structure ? 0.0 : 3.0 * c->cov_seen));
     const double sigma2 = dof > 0 ? sse / dof : 0.0;
     if (info) {
-        const double scratch = sel ? 8.0 * 3.0 * 32.0 * 32.0 * (double)d.nt32
+        const double scratch = sel ? 8.0 * 3.0 * 32.0 * 32.0 * (double)d.chol->plan.nt32
                                    : 8.0 * (double)ld * (double)ld;
         const double v[8] = {sse, dof, sigma2, (double)nfixed, ms_a, ms_b, scratch, 0.0};
         std::memcpy(info, v, sizeof v);
@@ -1954,8 +1958,9 @@ int vlgba_covariance(vlgba_ctx *c, int scale, double *cov_a, double *cov_a_full,
 // the selected method runs on the camera-aligned cyclic reduction's factors
 static bool cov_selected_ok(const vlgba_ctx *c)
 {
-    return c->d.cr_nlev > 0 && c->d.cr32 && c->world == 1 && !c->comm && !c->host_allreduce &&
-           !c->d.ordered;
+    const ba_chol *ch = c->d.chol;   // (null in a stage-mode context: no factors)
+    return ch && ch->plan.cr_nlev > 0 && ch->plan.cr32 && c->world == 1 && !c->comm &&
+           !c->host_allreduce && !c->d.ordered;
 }
 
 int vlgba_set_covariance_method(vlgba_ctx *c, int kind)
@@ -2016,7 +2021,6 @@ int vlgba_set_jacobian(vlgba_ctx *c, int kind)
     // last solve folded in built the other one
     TRY(ba_launch_rotations(&c->d, c->d.a, c->d.rot));
     c->lin_valid = 0;
-    c->d.camupd_done = 0;
     return 0;
 }
 
@@ -2086,9 +2090,9 @@ int vlgba_get_step(vlgba_ctx *c, double *da, double *db)
 int vlgba_debug_force_status(vlgba_ctx *c, int word, int passes)
 {
     if (!c || word < 4 || word > 6 || passes < 0) return VLGBA_E_ARG;
-    if (word == 6)
-        c->d.debug_runner_fail = passes;
-    else
+    if (word == 6) {
+        if (c->d.chol) c->d.chol->debug_runner_fail = passes;
+    } else
         (word == 4 ? c->debug_pivots : c->debug_timeouts) = passes;
     return 0;
 }
@@ -2179,18 +2183,21 @@ int vlgba_plan_info(vlgba_ctx *c, long long *info, int len)
 {
     if (!c || !info) return VLGBA_E_ARG;
     const ba_dev &d = c->d;
-    const long long ne = d.cr_nlev ? d.plan->eptr[d.cr_nlev] : 0;
-    const long long nk = d.cr_nlev ? d.plan->kptr[d.cr_nlev] : 0;
+    // the solve's slots: zeros in a stage-mode context (no solve, no plan)
+    static const chol_plan no_plan;
+    const chol_plan &P = d.chol ? d.chol->plan : no_plan;
+    const long long ne = P.cr_nlev ? P.eptr[P.cr_nlev] : 0;
+    const long long nk = P.cr_nlev ? P.kptr[P.cr_nlev] : 0;
     const long long v[VLGBA_NPLAN] = {d.N,   d.n,    d.m,   d.na,         d.nch,  d.ns,
-                                      d.nes, d.ngrp, d.ngs, d.nge,        d.nb,   d.nt,
-                                      d.cr_nlev, ne, nk,    d.ordered,    d.ordered ? d.T : d.nterm_fast,
+                                      d.nes, d.ngrp, d.ngs, d.nge,        d.nb,   P.nt,
+                                      P.cr_nlev, ne, nk,    d.ordered,    d.ordered ? d.T : d.nterm_fast,
                                       d.blob_words, d.mfma,
-                                      d.cr_nlev ? (d.cr32 ? d.tb32 : 64) : 0,
-                                      d.ngrp_mf, c->pperm.empty() ? 0 : 1, d.nl, d.nd_np,
-                                      d.nd_np ? d.nt - d.nd_a0[d.nd_np] : 0,
-                                      (long long)d.fl_factor, (long long)d.fl_syrk,
-                                      (long long)d.fl_back, d.runner_runs, d.vinv_fold,
-                                      d.camupd_fold};
+                                      P.cr_nlev ? (P.cr32 ? P.tb32 : 64) : 0,
+                                      d.ngrp_mf, c->pperm.empty() ? 0 : 1, d.nl, P.nd_np,
+                                      P.nd_np ? P.nt - P.nd_a0[P.nd_np] : 0,
+                                      (long long)P.fl_factor, (long long)P.fl_syrk,
+                                      (long long)P.fl_back, d.chol ? d.chol->runner_runs : 0,
+                                      d.vinv_fold, d.camupd_fold};
     for (int k = 0; k < len && k < VLGBA_NPLAN; k++) info[k] = v[k];
     return VLGBA_NPLAN;
 }
@@ -2475,14 +2482,13 @@ static int mex3_impl(int model, int m, int n, int num_a, const double *W, const 
         if ((rc = ctx_alloc(c, &d.obs_vis, (size_t)N))) break;
         if ((rc = upload(d.obs_vis, ov.data(), ov.size(), d.stream))) break;
         if ((rc = upload(d.W, hW.data(), hW.size(), d.stream))) break;
-        d.camupd_done = 0;
         if ((rc = upload(d.da, da, (size_t)d.ld, d.stream))) break;
         if ((rc = upload(d.eB, eB, 3 * (size_t)n, d.stream))) break;
         if ((rc = upload(d.Vinv, Vinv, 9 * (size_t)n, d.stream))) break;
         if ((rc = upload(d.a, a, (size_t)d.ld, d.stream))) break;
         if ((rc = upload(d.b, b, 3 * (size_t)n, d.stream))) break;
         VLGBA_CHECK(hipMemsetAsync(d.eA, 0, sizeof(double) * d.ld, d.stream));
-        if ((rc = ba_launch_update(&d, 0.0, ba_flags{}))) break;
+        if ((rc = ba_launch_update(&d, 0.0, ba_flags{}, false))) break;
         if ((rc = download(db, d.db, 3 * (size_t)n, d.stream))) break;
         if ((rc = download(a_new, d.a_new, (size_t)d.ld, d.stream))) break;
         if ((rc = download(b_new, d.b_new, 3 * (size_t)n, d.stream))) break;

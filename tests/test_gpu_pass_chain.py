@@ -268,3 +268,48 @@ def test_camupd_fold_fallback_solves_launch_the_update(gpu, word, field):
     assert np.array_equal(r1[0][2], r0[0][2]) and np.array_equal(r1[0][3], r0[0][3])
     assert np.array_equal(r1[3], r0[3]), (r1[3], r0[3])
     assert all(np.array_equal(x, y) for x, y in zip(r1[4], r0[4]))
+
+
+def test_camupd_fold_across_entry_points(gpu):
+    """Whether a solve did the camera update is handed from that solve to the
+    update of the same pass and lives nowhere else, so solver code that runs
+    between passes cannot leave it behind: two steps, then the selected-inverse
+    covariance (the per-level factor launches alone, no back substitution, no
+    update), get_step and get_reduced_system, then two more steps -- fold on
+    against off, bit for bit.  The first two cameras are the pivot (the gauge
+    is fixed, as in test_camupd_fold_fix_masks), so the covariance succeeds and
+    is compared too."""
+    sc = _banded(m=33)
+    a, b = _start(sc, 6)
+    res = {}
+    for fold in (True, False):
+        ba = _make(gpu, sc, 6, dict(pivot="first2"),
+                   {} if fold else {"VLGBA_CAMUPD_FOLD": "0"})
+        assert ba.plan_info()["camupd_fold"] == int(fold)
+        ba.set_params(a, b)
+        sse = []
+        for _ in range(2):
+            i = ba.step(relinearize=False, update_lm=True)
+            sse.append((i.old_sse, i.new_sse))
+        cov = ba.covariance(scale=False, method="selected")
+        cov = (cov["cam"], cov["pts"])
+        da, db = ba.last_step()
+        jk, blocks, e_ = ba.reduced_system(dense=False)
+        for _ in range(2):
+            i = ba.step(relinearize=False, update_lm=True)
+            sse.append((i.old_sse, i.new_sse))
+        params = ba.get_params()
+        launches, _ = _launches(ba, "k_camera_update")
+        res[fold] = dict(sse=sse, cov=cov, step=(da, db), red=(blocks, e_), params=params,
+                         launches=launches)
+        ba.close()
+    r1, r0 = res[True], res[False]
+    print(f"CAMUPD entry points: sse {r1['sse']} | {r0['sse']}; k_camera_update launches "
+          f"{r1['launches']} | {r0['launches']}")
+    assert (r1["launches"], r0["launches"]) == (0, 1)
+    assert r1["sse"] == r0["sse"], (r1["sse"], r0["sse"])
+    assert all(np.array_equal(x, y) for x, y in zip(r1["params"], r0["params"]))
+    assert all(np.array_equal(x, y) for x, y in zip(r1["step"], r0["step"]))
+    assert all(np.array_equal(x, y) for x, y in zip(r1["red"], r0["red"]))
+    assert all(np.isfinite(x).all() for x in r1["cov"])
+    assert all(np.array_equal(x, y) for x, y in zip(r1["cov"], r0["cov"]))

@@ -1,5 +1,5 @@
 // Diagnostic: dependent-chain latency (cycles per operation, one wave) of the
-// operations on the Cholesky pivot chain (wave_factor16, ba_chol.hip):
+// operations on the Cholesky pivot chain (wave_factor16, ba_chol_tile.h):
 // v_fma_f64, v_mul_f64, v_rsq_f64, the DPP row broadcast of a double, and one
 // whole pivot step.  Not part of the library.
 // Build: hipcc -O3 --offload-arch=gfx950 -ffp-contract=off tools/ubench_chain.hip -o tools/build/ubench_chain

@@ -1,6 +1,9 @@
 // Diagnostic micro-benchmark of the Cholesky tile kernels (not part of the
 // library).  Build: hipcc -O3 --offload-arch=gfx950 -ffp-contract=off
-//   -I include -I bundleadjustmentmatlab_amd/csrc tools/ubench_chol.hip -o ubench_chol
+//   -I include -I bundleadjustmentmatlab_amd/csrc tools/ubench_chol.hip
+//   bundleadjustmentmatlab_amd/csrc/ba_chol_plan.cpp -o ubench_chol
+// (it launches k_factor_step, so it includes the kernels' file, whose host side
+// calls the planner)
 // Prints in-kernel cycle stamps of the phases of block_potrf_inv and the
 // wall time of k_factor_step on a 2-tile SPD matrix.
 #include "../bundleadjustmentmatlab_amd/csrc/ba_chol.hip"
@@ -172,7 +175,8 @@ int main()
         for (int it = 0; it < 20; it++) {
             hipMemcpy(S, S0, sizeof(double) * n * n, hipMemcpyDeviceToDevice);
             hipEventRecord(e0);
-            k_factor_step<<<2, 256, smem3>>>(S, n, 0, pan, 1, pan, 0, linv, rhs, y, st);
+            k_factor_step<<<2, 256, smem3>>>(S, n, 0, pan, 1, pan, 0, linv, rhs, y, st, nullptr, 0u,
+                                             0, 0, env_rm{});
             hipEventRecord(e1);
             hipEventSynchronize(e1);
             float ms;

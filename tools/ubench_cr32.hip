@@ -5,17 +5,7 @@
 // tiles already in LDS; median over repetitions.
 // Build: hipcc -O3 --offload-arch=gfx950 -ffp-contract=off -I include
 //   tools/ubench_cr32.hip -o tools/build/ubench_cr32
-#include "../bundleadjustmentmatlab_amd/csrc/ba_chol.hip"
-
-void kt_begin(ba_ktimer *, hipStream_t) {}
-void kt_end(ba_ktimer *, hipStream_t, int) {}
-void *ba_dmalloc(size_t bytes)
-{
-    void *p = nullptr;
-    return hipMalloc(&p, bytes) == hipSuccess ? p : nullptr;
-}
-void ba_dfree(void *p) { (void)hipFree(p); }
-int ba_ensure_dyn_lds(const void *, size_t) { return 0; }
+#include "../bundleadjustmentmatlab_amd/csrc/ba_chol_tile.h"
 
 #include <algorithm>
 #include <cstdio>

@@ -2,17 +2,7 @@
 // stamps of the phases of block_potrf_inv and k_cr_factor on one SPD tile.
 // Build: hipcc -O3 --offload-arch=gfx950 -ffp-contract=off -I include
 //   tools/ubench_crf.hip -o tools/ubench_crf
-#include "../bundleadjustmentmatlab_amd/csrc/ba_chol.hip"
-
-void kt_begin(ba_ktimer *, hipStream_t) {}
-void kt_end(ba_ktimer *, hipStream_t, int) {}
-// the library's caching allocator (ba_solver.cpp) is not linked here either
-void *ba_dmalloc(size_t bytes)
-{
-    void *p = nullptr;
-    return hipMalloc(&p, bytes) == hipSuccess ? p : nullptr;
-}
-void ba_dfree(void *p) { (void)hipFree(p); }
+#include "../bundleadjustmentmatlab_amd/csrc/ba_chol_tile.h"
 
 #include <cstdio>
 #include <cstdlib>

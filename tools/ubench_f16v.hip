@@ -1,4 +1,4 @@
-// Variants of the 16-row pivot-chain factor (ba_chol.hip: wave_factor16x) on
+// Variants of the 16-row pivot-chain factor (ba_chol_tile.h: wave_factor16x) on
 // one wave: cycles (s_memtime) per call and a bit-for-bit comparison of L,
 // L^-1 and the substituted vectors against the library's version.
 //   V1: per pivot, every broadcast of the column first (distinct registers),
@@ -8,21 +8,13 @@
 //       16-double column store per pivot; LDS reads leave the VALU issue)
 // Build: hipcc -O3 --offload-arch=gfx950 -ffp-contract=off -I include
 //        tools/ubench_f16v.hip -o tools/build/ubench_f16v
-#include "../bundleadjustmentmatlab_amd/csrc/ba_chol.hip"
+#include "../bundleadjustmentmatlab_amd/csrc/ba_chol_tile.h"
 
 #include <algorithm>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <vector>
-
-// host helpers of the library that ba_chol.hip's host code references (never
-// called here)
-void kt_begin(struct ba_ktimer *, hipStream_t) {}
-void kt_end(struct ba_ktimer *, hipStream_t, int) {}
-void *ba_dmalloc(size_t) { return nullptr; }
-int ba_ensure_dyn_lds(const void *, size_t) { return 0; }
-void ba_dfree(void *) {}
 
 template <int V>
 __device__ __forceinline__ bool wave_factor16v(double *As, double *Li, int o, vseg lo, vseg hi,
