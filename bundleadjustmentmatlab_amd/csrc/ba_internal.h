@@ -80,8 +80,9 @@ struct ba_loss {
     double c;
 };
 
-// the camera reduction's arguments (k_camera_reduce_chunks, or workgroups
-// appended to the MFMA Schur launch: every plan with MFMA groups)
+// the fast path's camera reduction's arguments (ba_camred_args): to
+// k_camera_reduce_chunks, or to the workgroups a pass appends to its MFMA Schur
+// launch (ba_launch_schur_fast's fold: every plan with MFMA groups)
 struct ba_camred {
     const int *cam_eptr, *cam_eslots;
     const double *upart;
@@ -94,6 +95,11 @@ struct ba_camred {
     double *sse_out, *sse_out2;
 };
 
+// What persists for the whole solve, and nothing else: no field is written by
+// one launcher in order to be read by a later one.  What one launch of a pass
+// leaves for another travels as arguments and results of the launchers
+// (ba_launch_schur_fast's fold and side_camred, ba_chol_solve's cam_updated,
+// ba_launch_update's publish / published) and lives in locals of the pass.
 struct ba_dev {
     int m, n, na, N, js;
     int device, ncu;   // HIP device ordinal and its CU count
@@ -149,8 +155,6 @@ struct ba_dev {
     int ordered;       // 1: sequential bit-exact kernels (k_damp_point + k_schur)
     int parity;        // ordered = 2: + sequential solve and LM scalars (bit-identical
                        // LM trajectory with the oracle)
-    ba_camred camred;            // this pass's camera reduction
-    int camred_pending;          // ... to run inside the MFMA Schur launch
     int mfma;          // fast path: 1 = some MFMA Schur chunks (k_schur_mfma: groups
                        // [0, ngrp_mf)), 0 = term lists only (k_schur_group)
     int no_mfma;       // option: force the term-list Schur kernel
@@ -236,21 +240,23 @@ struct ba_dev {
                        // adds its own partials)
     int dpg_lambda;    // this rank adds the lambda dp'dp part of the camera dpg
     struct ba_ktimer *kt;   // NULL unless kernel timing is enabled
-    hipStream_t stream;
-    // second stream: the camera reduction runs there, concurrently with V*^-1
-    // and the Schur chunks, when the pass is single-rank and untimed;
-    // k_schur_reduce (the first consumer of U / eA) waits for ev_join
+    hipStream_t stream;   // the library stream: never reassigned after setup
+    // second stream of untimed single-rank passes, forked and joined with the
+    // event pair: a plan without MFMA groups runs the camera reduction there,
+    // beside V*^-1 and the Schur chunks (lm_pass), a mixed plan its per-term
+    // groups beside the MFMA groups (ba_launch_schur_fast); k_schur_reduce,
+    // the first consumer of either, waits for ev_join.  The launchers that can
+    // run there take the stream as an argument.
     hipStream_t side;
     hipEvent_t ev_fork, ev_join;
-    int join_pending;
     // host-mapped pass results: [0..5] the scal slots, [7] the pass sequence
-    // number written last (k_publish); the host spins on it instead of a
+    // number written last (k_publish, or the update's final sums when
+    // ba_launch_update is asked to publish); the host spins on it instead of a
     // device-to-host copy + stream synchronisation
     volatile double *hres;     // host view
     double *hres_dev;          // device view
-    unsigned long long seq;
-    int publish_req, published;   // fold the publish into the update's final sums
-    unsigned *pub_cnt;            // device counter of k_sum_parts3's blocks (zeroed)
+    unsigned long long seq;    // sequence number of the last publish launched
+    unsigned *pub_cnt;         // device counter of k_sum_parts3's blocks (zeroed)
 };
 
 #define KT_B(d) \
@@ -263,15 +269,22 @@ struct ba_dev {
 // ---- ba_kernels.hip ----
 int ba_launch_rotations(ba_dev *d, const double *a, double *rot);
 int ba_launch_linearize(ba_dev *d, ba_flags f);
-// fuse = 1 (an LM pass whose MFMA Schur launch follows): only records the
-// reduction for that launch when the plan has MFMA groups
-int ba_launch_camera_reduce(ba_dev *d, ba_flags f, int fuse = 0);
+// the fast path's camera reduction of the current linearisation (host only,
+// launches nothing)
+ba_camred ba_camred_args(const ba_dev *d, ba_flags f);
+// U / eA (fast path: and the old SSE) now, on stream s: the library stream, or
+// d->side in an untimed pass
+int ba_launch_camera_reduce(ba_dev *d, ba_flags f, hipStream_t s);
 int ba_launch_damp_point(ba_dev *d, double lambda);
 int ba_launch_schur(ba_dev *d, double lambda);
 int ba_launch_assemble(ba_dev *d);
 // cam_updated: the solve directly before formed a_new / rot_new itself
-// (ba_chol_solve), so no k_camera_update; false after every other writer of da
-int ba_launch_update(ba_dev *d, double lambda, ba_flags f, bool cam_updated);
+// (ba_chol_solve), so no k_camera_update; false after every other writer of da.
+// publish: the final-sums launch (k_sum_parts3: the fused and chunked updates)
+// should also publish the pass's scalars to hres; *published (may be null)
+// says whether a launch did, else the caller's ba_launch_publish has to
+int ba_launch_update(ba_dev *d, double lambda, ba_flags f, bool cam_updated, bool publish,
+                     bool *published);
 int ba_launch_yeb(ba_dev *d);
 // per observation (internal order) at the current parameters: e [N][2] = x - x_hat
 // (unweighted), w [N], rho [N] of the context's loss; any pointer may be NULL
@@ -285,7 +298,11 @@ void ba_dfree(void *p);
 // after a re-solve: did one of the runner's own hand-offs time out?  Then the
 // runner is off for this context (1); 0: no; < 0: error (ba_chol.hip)
 int ba_env_runner_timed_out(ba_dev *d);
-int ba_launch_schur_fast(ba_dev *d, double lambda);   // fused damp + Vinv + Y + S + e_
+// fused damp + Vinv + Y + S + e_.  fold (or null): this pass's camera reduction,
+// run by m + 1 workgroups appended to the MFMA Schur launch (needs ngrp_mf >
+// 0).  side_camred: the side stream carries this pass's camera reduction, its
+// end recorded in ev_join, so k_schur_reduce waits for it
+int ba_launch_schur_fast(ba_dev *d, double lambda, const ba_camred *fold, bool side_camred);
 // long tracks: count (fill = 0, into cnt[nb]) / write (fill = 1, at lpair_ptr) the
 // per-block (obs, obs) pairs of k_schur_reduce (context setup)
 int ba_launch_long_pairs(ba_dev *d, int fill, int *cnt);

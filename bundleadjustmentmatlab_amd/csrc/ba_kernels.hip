@@ -2836,27 +2836,28 @@ int ba_launch_linearize(ba_dev *d, ba_flags f)
     return -(int)hipGetLastError();
 }
 
-int ba_launch_camera_reduce(ba_dev *d, ba_flags f, int fuse)
+ba_camred ba_camred_args(const ba_dev *d, ba_flags f)
+{
+    // sse_out, sse_out2: scal[0] and the old_sse slot after U | eA (all-reduced
+    // together with them)
+    return ba_camred{d->cam_eptr, d->cam_eslots, d->upart, d->m, f, d->pivot,
+                     d->U, d->eA, d->chsse, d->nch, d->scal + 0, d->eA + d->ld};
+}
+
+// (the timing brackets record on the library stream: only an untimed pass
+// launches on the side stream, and they do nothing then)
+int ba_launch_camera_reduce(ba_dev *d, ba_flags f, hipStream_t s)
 {
     const int bs = ((d->na * (d->na + 1) / 2 + d->na) + 63) / 64 * 64;
-    if (!d->ordered) {
-        // m camera workgroups + one for the SSE: scal[0] and the old_sse slot
-        // after U | eA (all-reduced together with them)
-        d->camred = ba_camred{d->cam_eptr, d->cam_eslots, d->upart, d->m, f, d->pivot,
-                              d->U, d->eA, d->chsse, d->nch, d->scal + 0, d->eA + d->ld};
-        if (fuse && d->ngrp_mf > 0) {   // run by this pass's MFMA Schur launch
-            d->camred_pending = 1;
-            return 0;
-        }
-        KT_B(d);
-        BA_DISPATCH(d->na, (k_camera_reduce_chunks<NA><<<d->m + 1, 256, 0, d->stream>>>(
-                               d->camred)));
-        KT_E(d, KT_CAMRED);
-        return -(int)hipGetLastError();
-    }
     KT_B(d);
-    BA_DISPATCH(d->na, (k_camera_reduce<NA><<<d->m, bs, 0, d->stream>>>(
-                           d->cam_ptr, d->cam_obs, d->jrec, d->m, f, d->pivot, d->U, d->eA)));
+    if (!d->ordered) {   // m camera workgroups + one for the SSE
+        BA_DISPATCH(d->na, (k_camera_reduce_chunks<NA><<<d->m + 1, 256, 0, s>>>(
+                               ba_camred_args(d, f))));
+    } else {
+        BA_DISPATCH(d->na, (k_camera_reduce<NA><<<d->m, bs, 0, s>>>(
+                               d->cam_ptr, d->cam_obs, d->jrec, d->m, f, d->pivot, d->U,
+                               d->eA)));
+    }
     KT_E(d, KT_CAMRED);
     return -(int)hipGetLastError();
 }
@@ -2883,11 +2884,13 @@ int ba_launch_schur(ba_dev *d, double lambda)
 }
 
 template <int NA>
-static int launch_schur_fast(ba_dev *d, double lambda)
+static int launch_schur_fast(ba_dev *d, double lambda, const ba_camred *fold, bool side_camred)
 {
-    // MFMA groups [0, ngrp_mf), then the per-term groups [ngrp_mf, ngrp)
-    const bool two = d->ngrp_mf > 0 && d->ngrp > d->ngrp_mf &&
-                     !d->join_pending && d->side && !(d->kt && d->kt->on);
+    // MFMA groups [0, ngrp_mf), then the per-term groups [ngrp_mf, ngrp): in
+    // an untimed pass on two streams (a plan with MFMA groups folds its camera
+    // reduction, so the side stream is idle: side_camred implies ngrp_mf == 0)
+    const bool two = d->ngrp_mf > 0 && d->ngrp > d->ngrp_mf && d->side &&
+                     !(d->kt && d->kt->on);
     if (d->ngrp_mf > 0) {
         // vinv_fold: every point's V*^-1 is formed by its own MFMA group
         if (!d->vinv_fold) {
@@ -2902,13 +2905,13 @@ static int launch_schur_fast(ba_dev *d, double lambda)
         if (d->vinv_fold && sm2 < sizeof(double) * 256 * 9)   // the V rows' stage
             sm2 = sizeof(double) * 256 * 9;
         TRY_RC(ba_ensure_dyn_lds((const void *)k_schur_mfma<NA>, sm2));
-        const int ncr = d->camred_pending ? d->m + 1 : 0;
-        d->camred_pending = 0;
+        // the workgroups past the groups are the only readers of the struct
+        const int ncr = fold ? d->m + 1 : 0;
         KT_B(d);
         k_schur_mfma<NA><<<d->ngrp_mf + ncr, 256, sm2, d->stream>>>(
             d->grp_ch, d->grp_gs, d->grp_ge, d->ch_pt, d->ch_obase, d->ch_blob, d->blob, d->W,
             d->Vinv, d->eB, d->N, d->n, d->mf_max_s, d->mf_max_e, d->spart, d->epart,
-            d->ngrp_mf, d->camred, d->vinv_fold ? d->V : nullptr, lambda);
+            d->ngrp_mf, fold ? *fold : ba_camred{}, d->vinv_fold ? d->V : nullptr, lambda);
         KT_E(d, KT_SCHUR_MF);
     }
     if (d->ngrp > d->ngrp_mf) {
@@ -2920,24 +2923,16 @@ static int launch_schur_fast(ba_dev *d, double lambda)
         TRY_RC(ba_ensure_dyn_lds((const void *)k_schur_group<NA>, smem));
         // beside the MFMA groups on the side stream (disjoint partial slots;
         // V*^-1 is ready): the two launches' tails overlap.  Untimed passes
-        // only, and only when the side stream is idle (its camera reduction
-        // ran inside k_schur_mfma); k_schur_reduce joins below.
-        hipStream_t s0 = d->stream;
-        if (two) {
-            VLGBA_CHECK(hipStreamWaitEvent(d->side, d->ev_fork, 0));
-            d->stream = d->side;
-        }
+        // only, so the timing bracket (library stream) does nothing then;
+        // k_schur_reduce joins below.
+        if (two) VLGBA_CHECK(hipStreamWaitEvent(d->side, d->ev_fork, 0));
         KT_B(d);
-        k_schur_group<NA><<<d->ngrp - d->ngrp_mf, 256, smem, d->stream>>>(
+        k_schur_group<NA><<<d->ngrp - d->ngrp_mf, 256, smem, two ? d->side : d->stream>>>(
             d->grp_ch + d->ngrp_mf, d->grp_gs + d->ngrp_mf, d->grp_ge + d->ngrp_mf, d->ch_pt,
             d->ch_obase, d->ch_blob, d->blob, d->V, d->eB, d->W, lambda, bcap, gcap, ecap,
             d->Vinv, d->spart, d->epart);
         KT_E(d, KT_SCHUR_CHUNK);
-        if (two) {
-            d->stream = s0;
-            VLGBA_CHECK(hipEventRecord(d->ev_join, d->side));
-            d->join_pending = 1;
-        }
+        if (two) VLGBA_CHECK(hipEventRecord(d->ev_join, d->side));
     }
     if (d->nl > 0) {   // long tracks: their V*^-1, then their (obs, obs) tiles
         KT_B(d);
@@ -2950,10 +2945,9 @@ static int launch_schur_fast(ba_dev *d, double lambda)
         KT_E(d, KT_SCHUR_CHUNK);
     }
     const int bs = ((NA * NA + NA) + 63) / 64 * 64;
-    if (d->join_pending) {   // U / eA from the side stream's camera reduction
-        VLGBA_CHECK(hipStreamWaitEvent(d->stream, d->ev_join, 0));
-        d->join_pending = 0;
-    }
+    // U / eA from the side stream's camera reduction, or the per-term groups'
+    // partials
+    if (side_camred || two) VLGBA_CHECK(hipStreamWaitEvent(d->stream, d->ev_join, 0));
     KT_B(d);
     ba_longs lg{};
     if (d->nl > 0 && !d->nlb) {
@@ -2983,16 +2977,12 @@ int ba_launch_long_pairs(ba_dev *d, int fill, int *cnt)
     return -(int)hipGetLastError();
 }
 
-int ba_launch_schur_fast(ba_dev *d, double lambda)
+int ba_launch_schur_fast(ba_dev *d, double lambda, const ba_camred *fold, bool side_camred)
 {
-    switch (d->na) {
-    case 6: return launch_schur_fast<6>(d, lambda);
-    case 7: return launch_schur_fast<7>(d, lambda);
-    case BA_RAD_NA: return launch_schur_fast<BA_RAD_NA>(d, lambda);
-    case 10: return launch_schur_fast<10>(d, lambda);
-    case BA_PROJ_NA: return launch_schur_fast<BA_PROJ_NA>(d, lambda);
-    default: return -1000;
-    }
+    if (fold && d->ngrp_mf <= 0) return -1000;   // no launch to append it to
+    int rc = 0;
+    BA_DISPATCH(d->na, rc = launch_schur_fast<NA>(d, lambda, fold, side_camred));
+    return rc;
 }
 
 // the pass's scalars to host-mapped memory, the sequence number after them
@@ -3070,7 +3060,7 @@ static int launch_long_db(ba_dev *d, double lambda)
 // folded, from da and eA by k_sum_parts3's third block itself
 // (ba_sum3::cam_da).  A requested publish rides on it.
 static int launch_final_sums(ba_dev *d, const double *sse_part, const double *dpg_part, int gc,
-                             double lam_dpg, bool folded)
+                             double lam_dpg, bool folded, bool publish)
 {
     ba_sum3 s3 = {{sse_part, dpg_part, d->part},
                   {d->nch, d->nch, gc},
@@ -3084,12 +3074,10 @@ static int launch_final_sums(ba_dev *d, const double *sse_part, const double *dp
         s3.cam_na = d->na;
         s3.cam_lambda = lam_dpg;
     }
-    if (d->publish_req) {
+    if (publish) {
         d->seq++;
         s3.hres = d->hres_dev;
         s3.seq = (double)d->seq;
-        d->publish_req = 0;
-        d->published = 1;
     }
     k_sum_parts3<<<3, 1024, 0, d->stream>>>(s3);
     return -(int)hipGetLastError();
@@ -3104,13 +3092,17 @@ static int launch_final_sums(ba_dev *d, const double *sse_part, const double *dp
 // pass's own linearisation (App. A Q12).  Chunked (VLGBA_FUSED=0): the same
 // with k_point_update_chunk for the one pass and no linearisation.  Else the
 // per-point update and its three sums.
-int ba_launch_update(ba_dev *d, double lambda, ba_flags f, bool cam_updated)
+int ba_launch_update(ba_dev *d, double lambda, ba_flags f, bool cam_updated, bool publish,
+                     bool *published)
 {
     // cam_updated: the one-launch CR that ran directly before did the camera
     // update (ba_chol_solve), on the paths whose final sums are k_sum_parts3 --
     // every other update launches k_camera_update
     const bool chunked = !d->ordered && d->nch > 0 && !d->obs_vis && !d->xh_out;
     const bool folded = cam_updated && (d->fused || chunked);
+    // the publish rides on k_sum_parts3; the per-point update has three sums
+    publish = publish && (d->fused || chunked);
+    if (published) *published = publish;
     const int gc = (d->m + 63) / 64;
     // lambda dp'dp once over the ranks (each adds da' eA of its partial eA)
     const double lam_dpg = d->dpg_lambda ? lambda : 0.0;
@@ -3128,7 +3120,7 @@ int ba_launch_update(ba_dev *d, double lambda, ba_flags f, bool cam_updated)
         KT_E(d, KT_LIN_UPD);
         // (the new SSE = the new linearisation's SSE)
         return launch_final_sums(d, d->chsse2, d->chsse2 + 2 * (size_t)d->nch, gc, lam_dpg,
-                                 folded);
+                                 folded, publish);
     }
     if (chunked) {
         KT_B(d);
@@ -3153,7 +3145,7 @@ int ba_launch_update(ba_dev *d, double lambda, ba_flags f, bool cam_updated)
         }
         KT_E(d, KT_PTUPD);
         return launch_final_sums(d, d->chsse + d->nch, d->chsse + 2 * (size_t)d->nch, gc,
-                                 lam_dpg, folded);
+                                 lam_dpg, folded, publish);
     }
     k_sum_parts<<<1, BA_SUM_BS, 0, d->stream>>>(d->part, gc, d->scal + 2);
     const int g = grid_for(d->n, 256, PT_GRID_CAP);

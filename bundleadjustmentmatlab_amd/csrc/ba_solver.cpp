@@ -234,13 +234,13 @@ struct vlgba_ctx {
     double stop_rel = 1e-3;       // bundle_euclid.m:123 relative-decrease stop
     void (*on_pass)(int, int, const vlgba_step_info *, void *) = nullptr;
     void *on_pass_user = nullptr;
-    // pinv fallback of the reduced solve (allocated on first use)
     // internal point order (fast path, one rank): the short-track points that
     // fit the MFMA Schur chunks first, then the rest, each in input order.
     // pperm[new] = input point, operm[new obs] = input observation (point-major
     // input order), both relative to this rank's first point / observation;
     // empty = identity.
     std::vector<int> pperm, operm;
+    // pinv fallback of the reduced solve (allocated on first use)
     double *pinv_S = nullptr, *pinv_ev = nullptr, *pinv_e = nullptr, *pinv_w = nullptr;
     int *pinv_info = nullptr;
     int pinv_used = 0;            // passes that took the pinv fallback
@@ -762,17 +762,15 @@ static int ctx_setup(vlgba_ctx *c, const vlgba_problem *p, const host_obs &h,
     }
     TRY(ctx_alloc(c, &d.part, 3 * (size_t)BA_PART_MAX));
     TRY(ctx_alloc(c, &d.scal, 8));
-    if (p->num_obs > 0 || true) {
-        TRY(upload(d.obs_cam, lcam.data(), d.N, s));
-        TRY(upload(d.pt_ptr, lptr.data(), d.n + 1, s));
-        TRY(upload(d.cam_ptr, cptr.data(), p->m + 1, s));
-        TRY(upload(d.cam_obs, cobs.data(), d.N, s));
-        TRY(upload(d.obs_x, h.x.data() + 2 * o0, 2 * (size_t)d.N, s));
-        if (p->K) TRY(upload(d.K4, p->K, 4 * (size_t)p->m, s));
-        else VLGBA_CHECK(hipMemsetAsync(d.K4, 0, sizeof(double) * 4 * p->m, s));
-        TRY(upload(d.blk_ptr, hb.ptr.data(), hb.ptr.size(), s));
-        TRY(upload(d.term, hb.term.data(), hb.term.size(), s));
-    }
+    TRY(upload(d.obs_cam, lcam.data(), d.N, s));
+    TRY(upload(d.pt_ptr, lptr.data(), d.n + 1, s));
+    TRY(upload(d.cam_ptr, cptr.data(), p->m + 1, s));
+    TRY(upload(d.cam_obs, cobs.data(), d.N, s));
+    TRY(upload(d.obs_x, h.x.data() + 2 * o0, 2 * (size_t)d.N, s));
+    if (p->K) TRY(upload(d.K4, p->K, 4 * (size_t)p->m, s));
+    else VLGBA_CHECK(hipMemsetAsync(d.K4, 0, sizeof(double) * 4 * p->m, s));
+    TRY(upload(d.blk_ptr, hb.ptr.data(), hb.ptr.size(), s));
+    TRY(upload(d.term, hb.term.data(), hb.term.size(), s));
     ST_MARK("uploads");
     if (fast && d.nl > 0) {   // the long tracks' per-block pair lists (k_long_pairs)
         std::vector<int> h((size_t)d.nb + 1, 0);
@@ -999,8 +997,69 @@ static inline void mark(vlgba_ctx *c, int q)
     if (c->timing) (void)hipEventRecord(c->ev[q], c->d.stream);
 }
 
-// damping + V*^-1 + Y + Schur complement (S blocks, e_) and their all-reduce
-static int schur_phase(vlgba_ctx *c, double lam)
+// where stage 1 runs the camera reduction
+enum camred_route {
+    CAMRED_PLAIN,   // its own launch on the library stream
+    CAMRED_SIDE,    // its own launch on the side stream, beside V*^-1 and the Schur
+                    // chunks of the Schur phase that follows
+    CAMRED_FOLD     // workgroups of the MFMA Schur launch that follows
+};
+// what stage 1 left for the Schur phase of the same pass (CAMRED_SIDE,
+// CAMRED_FOLD); the default: nothing
+struct stage1_left {
+    bool fold = false;          // run the reduction fold_args inside the MFMA Schur launch
+    ba_camred fold_args{};
+    bool side_camred = false;   // join the side stream before k_schur_reduce
+};
+
+// Stage 1 at the current parameters: brings the context to "linearised, U /
+// eA and the old SSE in place" (lin_valid, no camera reduction due).
+// Linearises if the context holds no linearisation, or if relinearize and
+// the update is not the fused one: the fused update linearises every pass at
+// the new point (into the second buffers, swapped in on accept), so a pass
+// linearises here only after set_params, and relinearize then means the
+// camera reduction of the current linearisation (the rest of stage 1), the
+// work an accepted pass does.  The rotation table of d.a is current whenever
+// this runs: set_params and set_jacobian build it, an accepted step swaps in
+// the one built for a_new, and nothing else writes d.a.  Only a pass routes
+// the reduction off the library stream, and then passes `left` on to its
+// Schur phase.
+static int stage1(vlgba_ctx *c, int relinearize, camred_route route, stage1_left *left)
+{
+    ba_dev &d = c->d;
+    const bool full = !c->lin_valid || (relinearize && !d.fused);
+    if (full) TRY(ba_launch_linearize(&d, c->flags));
+    mark(c, 1);
+    if (!full && !relinearize && !c->camred_due) return 0;
+    if (route == CAMRED_FOLD) {
+        left->fold = true;
+        left->fold_args = ba_camred_args(&d, c->flags);
+    } else if (route == CAMRED_SIDE) {
+        // (no collective in between at world size 1)
+        VLGBA_CHECK(hipEventRecord(d.ev_fork, d.stream));
+        VLGBA_CHECK(hipStreamWaitEvent(d.side, d.ev_fork, 0));
+        TRY(ba_launch_camera_reduce(&d, c->flags, d.side));
+        VLGBA_CHECK(hipEventRecord(d.ev_join, d.side));
+        left->side_camred = true;
+    } else {
+        TRY(ba_launch_camera_reduce(&d, c->flags, d.stream));
+    }
+    // parity mode: the old SSE again, summed in the reference's flat order
+    if (d.parity) TRY(ba_launch_parity_old_sse(&d));
+    // U | eA | old_sse travel in one all-reduce (the fast path's reduce
+    // kernel writes the old_sse slot itself)
+    if (d.ordered)
+        VLGBA_CHECK(hipMemcpyAsync(d.eA + d.ld, d.scal + 0, sizeof(double),
+                                   hipMemcpyDeviceToDevice, d.stream));
+    c->lin_valid = 1;
+    c->camred_due = 0;
+    return 0;
+}
+
+// damping + V*^-1 + Y + Schur complement (S blocks, e_) and their all-reduce;
+// left: what this pass's stage 1 handed over (the recovery paths, the getters
+// and the covariance: nothing)
+static int schur_phase(vlgba_ctx *c, double lam, const stage1_left &left = {})
 {
     ba_dev &d = c->d;
     mark(c, 2);
@@ -1010,7 +1069,8 @@ static int schur_phase(vlgba_ctx *c, double lam)
         TRY(ba_launch_schur(&d, lam));
     } else {
         mark(c, 3);
-        TRY(ba_launch_schur_fast(&d, lam));
+        TRY(ba_launch_schur_fast(&d, lam, left.fold ? &left.fold_args : nullptr,
+                                 left.side_camred));
     }
     if (c->world > 1 || c->comm) {
         // [S blocks | e_ | old SSE] of this rank's points -> the global system
@@ -1025,8 +1085,9 @@ static int schur_phase(vlgba_ctx *c, double lam)
 }
 
 // the pass scalars after the update: cross-rank sums, then to the host (spin
-// on the host-mapped block when single-rank and untimed, else a copy)
-static int collect_scalars(vlgba_ctx *c, bool spin, double hs[6])
+// on the host-mapped block when single-rank and untimed, else a copy).
+// published: the update's final sums already publish them (ba_launch_update)
+static int collect_scalars(vlgba_ctx *c, bool spin, bool published, double hs[6])
 {
     ba_dev &d = c->d;
     // new SSE, camera and point parts of dp'(lambda dp + g), and the solve's
@@ -1038,7 +1099,7 @@ static int collect_scalars(vlgba_ctx *c, bool spin, double hs[6])
         // final sums, or k_publish); lower latency than a copy +
         // hipStreamSynchronize.  A stalled stream falls back to the
         // synchronisation, which reports the error
-        if (!d.published) TRY(ba_launch_publish(&d));
+        if (!published) TRY(ba_launch_publish(&d));
         const double want = (double)d.seq;
         const auto t0 = std::chrono::steady_clock::now();
         bool got = false;
@@ -1069,11 +1130,9 @@ static int collect_scalars(vlgba_ctx *c, bool spin, double hs[6])
 static int recovery_update(vlgba_ctx *c, double lam, double hs[6])
 {
     ba_dev &d = c->d;
-    d.publish_req = 0;
-    d.published = 0;
-    TRY(ba_launch_update(&d, lam, c->flags, false));
+    TRY(ba_launch_update(&d, lam, c->flags, false, false, nullptr));
     if (d.parity) TRY(ba_launch_parity_new_sums(&d, lam));
-    return collect_scalars(c, false, hs);
+    return collect_scalars(c, false, false, hs);
 }
 
 // A hand-off spin of the one-launch solve gave up (timeout word scal[5]):
@@ -1138,11 +1197,6 @@ std::mutex g_rs_mu;
 std::map<int, rocblas_handle> g_rs_handle;   // per device
 }   // namespace
 
-// da = pinv(S) * e_ on the GPU (bundle_euclid.m:193) for a pass whose
-// Cholesky met a non-positive pivot: S and e_ again (the solve overwrote them
-// in place), the lower triangle of S assembled densely, rocSOLVER dsyevd,
-// then V diag(1/ev, |ev| > tol) V^T e_ (ba_pinv_apply), and the update with
-// that da.  Every rank runs it on the identical all-reduced system.
 // rocSOLVER, the dense scratch of the fallbacks and this device's handle
 static int rs_prepare(vlgba_ctx *c, rs_api **rs_out, rocblas_handle *hdl_out)
 {
@@ -1174,6 +1228,20 @@ static int rs_prepare(vlgba_ctx *c, rs_api **rs_out, rocblas_handle *hdl_out)
     return 0;
 }
 
+// dpotrf / dpotri (fn) on the lower triangle of the dense scratch, in place,
+// and its info word on the host.  The caller holds g_rs_mu and has set the
+// handle's stream.
+static int rs_factor_info(vlgba_ctx *c, rocblas_handle hdl, decltype(rs_api::potrf) fn, int *info)
+{
+    const rocblas_int ld = (rocblas_int)c->d.ld;
+    if (fn(hdl, rocblas_fill_lower, ld, c->pinv_S, ld, c->pinv_info) != rocblas_status_success)
+        return VLGBA_E_ARG;
+    VLGBA_CHECK(hipMemcpyAsync(info, c->pinv_info, sizeof *info, hipMemcpyDeviceToHost,
+                               c->d.stream));
+    VLGBA_CHECK(hipStreamSynchronize(c->d.stream));
+    return 0;
+}
+
 // A pass whose nested-dissection Cholesky met a non-positive pivot: the same
 // S (the Cholesky took it in place) is assembled densely in the natural
 // camera order and factored by rocSOLVER dpotrf before the pinv fallback is
@@ -1199,13 +1267,8 @@ static int nd_natural_retry(vlgba_ctx *c, double lam, double hs[6])
     int info = 0;
     {
         std::lock_guard<std::mutex> lk(g_rs_mu);
-        if (rs->set_stream(hdl, d.stream) != rocblas_status_success ||
-            rs->potrf(hdl, rocblas_fill_lower, (rocblas_int)ld, c->pinv_S, (rocblas_int)ld,
-                      c->pinv_info) != rocblas_status_success)
-            return VLGBA_E_ARG;
-        VLGBA_CHECK(hipMemcpyAsync(&info, c->pinv_info, sizeof info, hipMemcpyDeviceToHost,
-                                   d.stream));
-        VLGBA_CHECK(hipStreamSynchronize(d.stream));
+        if (rs->set_stream(hdl, d.stream) != rocblas_status_success) return VLGBA_E_ARG;
+        TRY(rs_factor_info(c, hdl, rs->potrf, &info));
         if (info != 0) return 1;
         if (rs->potrs(hdl, rocblas_fill_lower, (rocblas_int)ld, 1, c->pinv_S, (rocblas_int)ld,
                       c->pinv_e, (rocblas_int)ld) != rocblas_status_success)
@@ -1221,6 +1284,11 @@ static int nd_natural_retry(vlgba_ctx *c, double lam, double hs[6])
     return 0;
 }
 
+// da = pinv(S) * e_ on the GPU (bundle_euclid.m:193) for a pass whose
+// Cholesky met a non-positive pivot: S and e_ again (the solve overwrote them
+// in place), the lower triangle of S assembled densely, rocSOLVER dsyevd,
+// then V diag(1/ev, |ev| > tol) V^T e_ (ba_pinv_apply), and the update with
+// that da.  Every rank runs it on the identical all-reduced system.
 static int pinv_fallback(vlgba_ctx *c, double lam, double hs[6])
 {
     ba_dev &d = c->d;
@@ -1265,48 +1333,16 @@ static int lm_pass(vlgba_ctx *c, int relinearize, vlgba_step_info *info)
     ba_dev &d = c->d;
     const double lam = c->lambda;
     mark(c, 0);
-    // fused update: every pass's update linearises at the new point (into the
-    // second buffers, swapped in on accept), so a pass linearises here only
-    // after set_params; relinearize then means the camera reduction of the
-    // current linearisation (the rest of stage 1), the work an accepted pass
-    // does
-    const bool full = !c->lin_valid || (relinearize && !d.fused);
-    if (full || (d.fused && (relinearize || c->camred_due))) {
-        // the rotation table of d.a is current: set_params builds it and an
-        // accepted step swaps in the one k_camera_update built for a_new
-        if (full) TRY(ba_launch_linearize(&d, c->flags));
-        mark(c, 1);
-        if (!d.ordered && d.ngrp_mf > 0) {
-            // U / eA / old SSE: workgroups of this pass's MFMA Schur launch
-            TRY(ba_launch_camera_reduce(&d, c->flags, 1));
-        } else if (!d.ordered && c->world == 1 && !c->timing) {
-            // U / eA / old SSE on the side stream, overlapping V*^-1 and the
-            // Schur chunks (no collective in between at world size 1);
-            // launch_schur_fast joins before k_schur_reduce
-            VLGBA_CHECK(hipEventRecord(d.ev_fork, d.stream));
-            VLGBA_CHECK(hipStreamWaitEvent(d.side, d.ev_fork, 0));
-            hipStream_t s0 = d.stream;
-            d.stream = d.side;
-            const int rc = ba_launch_camera_reduce(&d, c->flags);
-            d.stream = s0;
-            TRY(rc);
-            VLGBA_CHECK(hipEventRecord(d.ev_join, d.side));
-            d.join_pending = 1;
-        } else {
-            TRY(ba_launch_camera_reduce(&d, c->flags));
-        }
-        if (d.parity) TRY(ba_launch_parity_old_sse(&d));
-        // U | eA | old_sse travel in one all-reduce (the fast path's reduce
-        // kernel writes the old_sse slot itself)
-        if (d.ordered)
-            VLGBA_CHECK(hipMemcpyAsync(d.eA + d.ld, d.scal + 0, sizeof(double),
-                                       hipMemcpyDeviceToDevice, d.stream));
-        c->lin_valid = 1;
-        c->camred_due = 0;
-    } else {
-        mark(c, 1);
-    }
-    TRY(schur_phase(c, lam));
+    // U / eA / old SSE of a relinearised pass: workgroups of this pass's MFMA
+    // Schur launch when the plan has MFMA groups; else, single-rank and
+    // untimed, on the side stream (ba_launch_schur_fast joins before
+    // k_schur_reduce); else a launch of their own
+    const camred_route route = !d.ordered && d.ngrp_mf > 0 ? CAMRED_FOLD
+                               : !d.ordered && c->world == 1 && !c->timing ? CAMRED_SIDE
+                                                                           : CAMRED_PLAIN;
+    stage1_left left;
+    TRY(stage1(c, relinearize, route, &left));
+    TRY(schur_phase(c, lam, left));
     mark(c, 4);
     TRY(ba_launch_assemble(&d));
     mark(c, 5);
@@ -1325,16 +1361,15 @@ static int lm_pass(vlgba_ctx *c, int relinearize, vlgba_step_info *info)
     // RCCL ranks spin as well: their collectives are stream-ordered, and the
     // publish then follows the scalars' all-reduce (collect_scalars)
     const bool spin = (c->world == 1 || c->comm) && !c->timing;
-    d.publish_req = spin && !c->comm;   // the fast update's final-sums launch publishes
-    d.published = 0;
-    TRY(ba_launch_update(&d, lam, c->flags, cam_updated));
-    d.publish_req = 0;
+    // (without RCCL the fast update's final-sums launch publishes)
+    bool published = false;
+    TRY(ba_launch_update(&d, lam, c->flags, cam_updated, spin && !c->comm, &published));
     if (d.parity) TRY(ba_launch_parity_new_sums(&d, lam));
     mark(c, 7);
     // scalars: [0] old_sse [1] new_sse [2] dpg cameras [3] dpg points
     // [4] non-positive pivot [5] hand-off spin timeout (summed over ranks)
     double hs[6];
-    TRY(collect_scalars(c, spin, hs));
+    TRY(collect_scalars(c, spin, published, hs));
     info->pinv = 0;
     info->spin_retry = 0;
     info->nd_retry = 0;
@@ -1619,18 +1654,7 @@ int vlgba_get_linearization(vlgba_ctx *c, double *U, double *eA, double *V, doub
     // the linearisation the context holds for the current parameters (a
     // rejected step's, or the one the fused update made at an accepted step's
     // new point), else a new one
-    if (!c->lin_valid) {
-        TRY(ba_launch_rotations(&d, d.a, d.rot));
-        TRY(ba_launch_linearize(&d, c->flags));
-    }
-    if (!c->lin_valid || c->camred_due) {
-        TRY(ba_launch_camera_reduce(&d, c->flags));
-        if (d.ordered)
-            VLGBA_CHECK(hipMemcpyAsync(d.eA + d.ld, d.scal + 0, sizeof(double),
-                                       hipMemcpyDeviceToDevice, d.stream));
-    }
-    c->lin_valid = 1;
-    c->camred_due = 0;
+    TRY(stage1(c, 0, CAMRED_PLAIN, nullptr));
     // U / eA stay per-rank partials on the device (schur_owner); the caller
     // gets their sum over ranks
     const size_t nue = (size_t)d.na * d.na * d.m + d.ld + 1;
@@ -1676,20 +1700,8 @@ int vlgba_get_reduced_system(vlgba_ctx *c, int *blk_jk, double *blocks, double *
     if (!c) return VLGBA_E_ARG;
     TRY(ctx_enter(c));
     ba_dev &d = c->d;
-    if (!c->lin_valid || c->camred_due) {   // stage 1 at the current parameters (as a
-        if (!c->lin_valid) TRY(ba_launch_linearize(&d, c->flags));   // pass would)
-        TRY(ba_launch_camera_reduce(&d, c->flags));
-        c->camred_due = 0;
-        if (d.ordered)
-            VLGBA_CHECK(hipMemcpyAsync(d.eA + d.ld, d.scal + 0, sizeof(double),
-                                       hipMemcpyDeviceToDevice, d.stream));
-        c->lin_valid = 1;
-    }
+    TRY(stage1(c, 0, CAMRED_PLAIN, nullptr));
     TRY(schur_phase(c, c->lambda));
-    if (d.join_pending) {
-        VLGBA_CHECK(hipStreamWaitEvent(d.stream, d.ev_join, 0));
-        d.join_pending = 0;
-    }
     if (blk_jk) TRY(download(blk_jk, d.blk_jk, 2 * (size_t)d.nb, d.stream));
     if (blocks) TRY(download(blocks, d.sblk, (size_t)d.na * d.na * d.nb, d.stream));
     if (e_) TRY(download(e_, d.rhs, (size_t)d.ld, d.stream));
@@ -1802,17 +1814,7 @@ static int cov_run(vlgba_ctx *c, int scale, double *cov_a, double *cov_a_full, d
     if (sel) TRY(cov_setup_selected(c));
     c->cov_have = 0;
     const long long ld = d.ld;
-    // stage 1 at the current parameters, as a pass would run it
-    if (!c->lin_valid || c->camred_due) {
-        if (!c->lin_valid) TRY(ba_launch_linearize(&d, c->flags));
-        TRY(ba_launch_camera_reduce(&d, c->flags));
-        if (d.parity) TRY(ba_launch_parity_old_sse(&d));
-        if (d.ordered)
-            VLGBA_CHECK(hipMemcpyAsync(d.eA + d.ld, d.scal + 0, sizeof(double),
-                                       hipMemcpyDeviceToDevice, d.stream));
-        c->lin_valid = 1;
-        c->camred_due = 0;
-    }
+    TRY(stage1(c, 0, CAMRED_PLAIN, nullptr));
     hipEvent_t ev[3] = {};
     for (auto &e : ev) VLGBA_CHECK(hipEventCreate(&e));
     // the selected method: S0 in the CR's tiles as a pass assembles it (unit
@@ -1822,10 +1824,6 @@ static int cov_run(vlgba_ctx *c, int scale, double *cov_a, double *cov_a_full, d
     auto run_selected = [&]() -> int {
         VLGBA_CHECK(hipEventRecord(ev[0], d.stream));
         TRY(schur_phase(c, 0.0));
-        if (d.join_pending) {
-            VLGBA_CHECK(hipStreamWaitEvent(d.stream, d.ev_join, 0));
-            d.join_pending = 0;
-        }
         TRY(ba_launch_assemble(&d));
         TRY(ba_cov_mark_fixed_blocks(&d, c->cov_fixed));
         TRY(ba_cr32_factor(&d));
@@ -1847,10 +1845,6 @@ static int cov_run(vlgba_ctx *c, int scale, double *cov_a, double *cov_a_full, d
         // S0: the undamped Schur phase (it also leaves V+ = vlg_pinv3(V) in d.Vinv),
         // dense lower triangle, unit diagonal on the exactly-zero rows
         TRY(schur_phase(c, 0.0));
-        if (d.join_pending) {
-            VLGBA_CHECK(hipStreamWaitEvent(d.stream, d.ev_join, 0));
-            d.join_pending = 0;
-        }
         TRY(ba_launch_assemble_plain(&d, c->pinv_S, ld, 1));
         TRY(ba_cov_mark_fixed(&d, c->pinv_S, ld, c->cov_fixed));
         TRY(ba_fix_diag_plain(&d, c->pinv_S, ld));
@@ -1859,21 +1853,11 @@ static int cov_run(vlgba_ctx *c, int scale, double *cov_a, double *cov_a_full, d
         {
             std::lock_guard<std::mutex> lk(g_rs_mu);
             int pinfo = 0;
-            if (rs->set_stream(hdl, d.stream) != rocblas_status_success ||
-                rs->potrf(hdl, rocblas_fill_lower, (rocblas_int)ld, c->pinv_S, (rocblas_int)ld,
-                          c->pinv_info) != rocblas_status_success)
-                return VLGBA_E_ARG;
-            VLGBA_CHECK(hipMemcpyAsync(&pinfo, c->pinv_info, sizeof pinfo, hipMemcpyDeviceToHost,
-                                       d.stream));
-            VLGBA_CHECK(hipStreamSynchronize(d.stream));
-            if (pinfo != 0) return VLGBA_E_SINGULAR;
-            if (rs->potri(hdl, rocblas_fill_lower, (rocblas_int)ld, c->pinv_S, (rocblas_int)ld,
-                          c->pinv_info) != rocblas_status_success)
-                return VLGBA_E_ARG;
-            VLGBA_CHECK(hipMemcpyAsync(&pinfo, c->pinv_info, sizeof pinfo, hipMemcpyDeviceToHost,
-                                       d.stream));
-            VLGBA_CHECK(hipStreamSynchronize(d.stream));
-            if (pinfo != 0) return VLGBA_E_SINGULAR;
+            if (rs->set_stream(hdl, d.stream) != rocblas_status_success) return VLGBA_E_ARG;
+            for (auto fn : {rs->potrf, rs->potri}) {
+                TRY(rs_factor_info(c, hdl, fn, &pinfo));
+                if (pinfo != 0) return VLGBA_E_SINGULAR;
+            }
         }
         TRY(ba_cov_finish(&d, c->pinv_S, ld, c->cov_fixed, c->cov_diag));
         if (c->cov_src_packed)
@@ -2353,7 +2337,7 @@ static int mex1_impl(int model, int m, int n, int num_a, const double *K, const 
         ba_flags f = {0, 0, 0};
         if ((rc = ba_launch_rotations(&d, d.a, d.rot))) break;
         if ((rc = ba_launch_linearize(&d, f))) break;
-        if ((rc = ba_launch_camera_reduce(&d, f))) break;
+        if ((rc = ba_launch_camera_reduce(&d, f, d.stream))) break;
         if ((rc = download(jr.data(), d.jrec, jr.size(), d.stream))) break;
         if ((rc = download(hW.data(), d.W, hW.size(), d.stream))) break;
         if ((rc = download(xh.data(), d.xh_out, xh.size(), d.stream))) break;
@@ -2488,7 +2472,7 @@ static int mex3_impl(int model, int m, int n, int num_a, const double *W, const 
         if ((rc = upload(d.a, a, (size_t)d.ld, d.stream))) break;
         if ((rc = upload(d.b, b, 3 * (size_t)n, d.stream))) break;
         VLGBA_CHECK(hipMemsetAsync(d.eA, 0, sizeof(double) * d.ld, d.stream));
-        if ((rc = ba_launch_update(&d, 0.0, ba_flags{}, false))) break;
+        if ((rc = ba_launch_update(&d, 0.0, ba_flags{}, false, false, nullptr))) break;
         if ((rc = download(db, d.db, 3 * (size_t)n, d.stream))) break;
         if ((rc = download(a_new, d.a_new, (size_t)d.ld, d.stream))) break;
         if ((rc = download(b_new, d.b_new, 3 * (size_t)n, d.stream))) break;

@@ -25,6 +25,13 @@ The thinned scene puts points no camera sees (V = 0: the zero block) and points
 seen once (rank-deficient V) inside the Schur groups' ranges; the posterior
 covariance's undamped Schur phase (lambda = 0) then takes vlg_pinv3's Jacobi
 branch for the latter inside the Schur launch.
+
+The last section holds what one launch of a pass leaves for another (the
+camera reduction to fold, the side stream's join, the publish) to the three
+plan kinds that route them differently: against the other entry points run
+between passes, timed against untimed passes, and -- stage 1 being one
+function for the pass, the getters and the covariance -- parity mode's
+sequential old SSE after a getter.
 """
 import os
 
@@ -313,3 +320,120 @@ def test_camupd_fold_across_entry_points(gpu):
     assert all(np.array_equal(x, y) for x, y in zip(r1["red"], r0["red"]))
     assert all(np.isfinite(x).all() for x in r1["cov"])
     assert all(np.array_equal(x, y) for x, y in zip(r1["cov"], r0["cov"]))
+
+
+# ---- what one launch of a pass leaves for another --------------------------
+# The three ways a pass routes its camera reduction and Schur launches
+# (plan_info): every group an MFMA group (the reduction's workgroups and the
+# publish ride on the pass's own launches), the per-term kernel alone (the
+# reduction on the side stream, joined before k_schur_reduce), both kinds (the
+# per-term groups on the side stream beside the MFMA groups).
+PLAN_KINDS = ("mfma", "term", "mixed")
+
+
+def _plan_kind_ctx(gpu, kind, sc=None):
+    sc = sc or (_long() if kind == "mixed" else _banded())
+    kw = dict(pivot="first2")              # the gauge fixed: the covariance exists
+    if kind == "term":
+        kw["schur_kernel"] = "terms"
+    ba = _make(gpu, sc, 6, kw, {})
+    p = ba.plan_info()
+    assert p["ordered"] == 0 and p["groups"] > 1, p
+    if kind == "mfma":
+        assert p["mfma_groups"] == p["groups"], p
+    elif kind == "term":
+        assert p["mfma_groups"] == 0 and p["mfma"] == 0, p
+    else:
+        assert 0 < p["mfma_groups"] < p["groups"], p
+    ba.set_params(*_start(sc, 6))
+    return ba
+
+
+def _pass_record(ba, relinearize):
+    i = ba.step(relinearize=relinearize, update_lm=True)
+    da, db = ba.last_step()
+    return (i.old_sse, i.new_sse, i.dpg, i.accepted, i.lambda_), da.copy(), db.copy()
+
+
+def _same_passes(ra, rb, what):
+    assert len(ra) == len(rb)
+    for k, (u, v) in enumerate(zip(ra, rb)):
+        assert u[0] == v[0], (what, k, u[0], v[0])
+        assert np.array_equal(u[1], v[1]) and np.array_equal(u[2], v[2]), (what, k)
+
+
+@pytest.mark.parametrize("kind", PLAN_KINDS)
+def test_handoffs_survive_the_entry_points_between_passes(gpu, kind):
+    """The camera reduction to fold, the side stream's join and the publish
+    are arguments and locals of one pass, so nothing another entry point
+    launches between two passes can leave one of them behind or consume it:
+    four applied passes and a relinearising one, alone and with
+    get_linearization, get_reduced_system, the dense covariance (an undamped
+    Schur phase on the same buffers) and get_step between every two of them
+    -- scalars, steps and final parameters bit for bit."""
+    res = {}
+    for between in (False, True):
+        ba = _plan_kind_ctx(gpu, kind)
+        recs = []
+        for k in range(5):
+            recs.append(_pass_record(ba, relinearize=(k == 4)))
+            if between and k < 4:
+                lin = ba.linearization()
+                S, e_ = ba.reduced_system(dense=False)[1:]
+                cov = ba.covariance(scale=False, method="dense")
+                da, db = ba.last_step()
+                assert np.array_equal(da, recs[-1][1]) and np.array_equal(db, recs[-1][2])
+                assert all(np.isfinite(x).all() for x in
+                           (lin["U"], lin["eA"], S, e_, cov["cam"], cov["pts"]))
+        res[between] = (recs, ba.get_params())
+        ba.close()
+    print(f"HANDOFFS {kind}: " + "; ".join(repr(r[0]) for r in res[True][0]))
+    _same_passes(res[True][0], res[False][0], kind)
+    assert all(np.array_equal(x, y) for x, y in zip(res[True][1], res[False][1])), kind
+
+
+@pytest.mark.parametrize("kind", PLAN_KINDS)
+def test_timed_and_untimed_passes_agree(gpu, kind):
+    """A timed pass launches nothing on the side stream, copies its scalars
+    instead of spinning on them and publishes nothing from the update's final
+    sums; the kernels and their inputs are the untimed pass's, so four
+    applied passes give the same scalars, steps and parameters bit for bit."""
+    res = {}
+    for timed in (False, True):
+        ba = _plan_kind_ctx(gpu, kind)
+        ba.set_timing(timed)
+        recs = [_pass_record(ba, relinearize=False) for _ in range(4)]
+        res[timed] = (recs, ba.get_params())
+        ba.close()
+    print(f"TIMED {kind}: " + "; ".join(repr(r[0]) for r in res[True][0]))
+    _same_passes(res[True][0], res[False][0], kind)
+    assert all(np.array_equal(x, y) for x, y in zip(res[True][1], res[False][1])), kind
+
+
+@pytest.mark.parametrize("getter", ["reduced_system", "linearization"])
+def test_parity_old_sse_after_a_getter(gpu, getter):
+    """Parity mode sums the old SSE sequentially in the reference's flat order
+    (k_seq_old_sse) wherever stage 1 runs.  A getter that runs stage 1 after
+    set_params marks the linearisation valid, so the step after it
+    (relinearize=False) runs no stage 1 of its own and reports the getter's old
+    SSE: the same digits as a step that runs stage 1 itself.
+
+    The library before the shared stage 1 left the getters' old SSE to
+    k_sum_parts' order; the figures of both libraries on this scene are in
+    profiles/pass_handoffs/README.md."""
+    from bundleadjustmentmatlab_amd.scene import make_config
+    sc = make_config("cfg1", m=6, min_n=30, max_n=60, seed=7)   # test_gpu_lm_parity's "small"
+    assert sc.n < 200
+    a, b = _start(sc, 6)
+    res = {}
+    for first in (getter, None):
+        ba = gpu.BundleAdjuster(sc.K, sc.obs_pt, sc.obs_cam, sc.obs_x, sc.n, 6, parity=True)
+        assert ba.plan_info()["ordered"] == 1
+        ba.set_params(a, b)
+        if first:
+            getattr(ba, first)()
+        i = ba.step(relinearize=False, update_lm=False)
+        res[first] = (repr(i.old_sse), repr(i.new_sse), repr(i.dpg))
+        ba.close()
+    print(f"PARITY old SSE after {getter}: {res[getter]} | alone {res[None]}")
+    assert res[getter] == res[None], (res[getter], res[None])
