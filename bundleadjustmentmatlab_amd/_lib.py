@@ -129,6 +129,15 @@ SIGNATURES = {
     "vlgba_intersect": (c_int, [c_int, c_dp, c_dp, c_dp, c_ll, ctypes.POINTER(c_ll), c_ip, c_dp,
                                 ctypes.POINTER(VlgbaOptions), c_dp, c_dp, c_int, c_ip,
                                 ctypes.POINTER(VlgbaStats)]),
+    "vlgba_resect_ex": (c_int, [ctypes.POINTER(VlgbaResectProblem), ctypes.POINTER(VlgbaOptions),
+                                c_int, c_int, c_double, c_dp, c_dp, c_int, c_ip, c_dp, c_dp,
+                                ctypes.POINTER(VlgbaStats)]),
+    "vlgba_intersect_ex": (c_int, [c_int, c_dp, c_dp, c_dp, c_dp, c_ll, ctypes.POINTER(c_ll), c_ip,
+                                   c_dp, ctypes.POINTER(VlgbaOptions), c_int, c_int, c_double,
+                                   c_dp, c_dp, c_int, c_ip, c_dp, c_dp,
+                                   ctypes.POINTER(VlgbaStats)]),
+    "vlgba_triangulate_ex": (c_int, [c_int, c_dp, c_dp, c_dp, c_dp, c_ll, ctypes.POINTER(c_ll),
+                                     c_ip, c_dp, c_int, c_dp, c_ip]),
     "vlgba_scene_banded": (c_int, [ctypes.POINTER(VlgbaSceneSpec), c_int,
                                    ctypes.POINTER(VlgbaSceneOut)]),
     "vlgba_version": (c_int, [ctypes.c_char_p, c_int]),

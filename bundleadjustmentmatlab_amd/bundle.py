@@ -741,8 +741,24 @@ def bundle_euclid_nomex(K, Te, w, Xe, x, *varargin, device=0, return_stats=False
                          loss_scale=loss_scale, covariance_method=covariance_method, **solver)
 
 
+def _block_mode(radial, jacobian, loss, loss_scale, return_residuals):
+    """(extended, jacobian kind, loss kind, scale) of the batched one-block
+    entries' mode keywords: extended is False with every keyword at its default
+    (the plain entry is called then, exactly as before).  jacobian None: "fd",
+    or "analytic" with radial= (that model has no other)."""
+    if jacobian is None:
+        jacobian = "fd" if radial is None else "analytic"
+    if jacobian not in JACOBIANS:
+        raise ValueError(f"jacobian must be one of {sorted(JACOBIANS)}, got {jacobian!r}")
+    if loss not in LOSSES:
+        raise ValueError(f"loss must be one of {sorted(LOSSES)}, got {loss!r}")
+    ex = radial is not None or jacobian != "fd" or loss != "none" or bool(return_residuals)
+    return ex, JACOBIANS[jacobian], LOSSES[loss], float(loss_scale)
+
+
 def bundle_euclid_resect(K, Te, w, Xs, xs, *varargin, device=0, max_iter=0, max_iter2=0,
-                         lambda0=0.0, stop_rel=0.0, return_stats=False):
+                         lambda0=0.0, stop_rel=0.0, return_stats=False, radial=None,
+                         jacobian=None, loss="none", loss_scale=0.0, return_residuals=False):
     """Batched one-camera refinement with the structure fixed -- the call of
     estimate_camera.m:247-253,
 
@@ -754,13 +770,25 @@ def bundle_euclid_resect(K, Te, w, Xs, xs, *varargin, device=0, max_iter=0, max_
     measured image points (2 or 3 x n_q; only the inliers).  Options as
     bundle_euclid.m: 'fix_calibration' (num_a 6), 'fix_principal' (7), neither
     (10); 'fix_structure' is implied.  Returns K_, Te_, w_ and the list of
-    per-camera error_ (SSE / n_q per accepted step)."""
+    per-camera error_ (SSE / n_q per accepted step).
+
+    Beyond the reference (vlgba_resect_ex; with all of them at their defaults
+    the call is vlgba_resect's, as before): ``radial`` = kd0 (2 x c start
+    coefficients k1; k2) refines the radial-distortion camera [w; T; f; k1; k2]
+    from the focal length K[0] (the calibration options do not apply; analytic
+    Jacobians only) and returns the refined 2 x c coefficients as an extra last
+    output; ``jacobian`` "fd" | "analytic"; ``loss`` "none" | "huber" |
+    "cauchy" at ``loss_scale`` pixels (error_ is then the robust cost / n_q);
+    ``return_residuals`` appends a list of (e (2 x n_q) the unweighted residuals
+    x - x_hat, w (n_q) the loss's weights) at the returned parameters.  Output
+    order: K_, Te_, w_, errs[, stats][, residuals][, kd_]."""
     K, Te, w = _F(K), _F(Te), _F(w)
     c = w.shape[1]
+    ex, jac, lk, ls = _block_mode(radial, jacobian, loss, loss_scale, return_residuals)
     o = parse_options(c, 0, varargin)
-    nvk = o["num_variableK"]
+    nvk = o["num_variableK"] if radial is None else RADIAL_NVK
     na = 6 + nvk
-    a = np.ascontiguousarray(pack_a(K, Te, w, nvk).reshape(-1, order="F"))
+    a = np.ascontiguousarray(pack_a(K, Te, w, nvk, radial).reshape(-1, order="F"))
     assert len(Xs) == len(xs) == c
     cnt = [np.shape(X)[1] for X in Xs]
     assert all(np.shape(x)[1] == k for x, k in zip(xs, cnt))
@@ -778,12 +806,27 @@ def bundle_euclid_resect(K, Te, w, Xs, xs, *varargin, device=0, max_iter=0, max_
     opt.max_iter, opt.max_iter2, opt.lambda0 = int(max_iter), int(max_iter2), float(lambda0)
     opt.device, opt.stop_rel = int(device), float(stop_rel)
     st = VlgbaStats()
-    check(lib().vlgba_resect(ctypes.byref(pr), ctypes.byref(opt), _dp(a), _dp(err), cap,
-                             nerr.ctypes.data_as(c_ip), ctypes.byref(st)), "vlgba_resect")
+    if not ex:
+        check(lib().vlgba_resect(ctypes.byref(pr), ctypes.byref(opt), _dp(a), _dp(err), cap,
+                                 nerr.ctypes.data_as(c_ip), ctypes.byref(st)), "vlgba_resect")
+    else:
+        res = np.zeros((int(ptr[-1]), 2))
+        wts = np.zeros(int(ptr[-1]))
+        check(lib().vlgba_resect_ex(ctypes.byref(pr), ctypes.byref(opt), jac, lk, ls, _dp(a),
+                                    _dp(err), cap, nerr.ctypes.data_as(c_ip),
+                                    _dp(res) if return_residuals else None,
+                                    _dp(wts) if return_residuals else None, ctypes.byref(st)),
+              "vlgba_resect_ex")
     a = a.reshape(na, c, order="F")
     K_, Te_, w_, _ = unpack(K, a, np.zeros((3, 0)), np.zeros((1, 0)), nvk)
     errs = [err[q, : nerr[q]].copy() for q in range(c)]
-    return (K_, Te_, w_, errs, st) if return_stats else (K_, Te_, w_, errs)
+    out = (K_, Te_, w_, errs) + ((st,) if return_stats else ())
+    if return_residuals:
+        out += ([(res[ptr[q]:ptr[q + 1]].T.copy(), wts[ptr[q]:ptr[q + 1]].copy())
+                 for q in range(c)],)
+    if radial is not None:
+        out += (a[7:9].copy(order="F"),)
+    return out
 
 
 def _tracks(K, Te, w, obs_ptr, obs_cam, obs_x):
@@ -803,7 +846,16 @@ def _tracks(K, Te, w, obs_ptr, obs_cam, obs_x):
     return keep, args
 
 
-def triangulate_points(K, Te, w, obs_ptr, obs_cam, obs_x, device=0, return_status=False):
+def _radial_kd(radial, m):
+    """radial= of the per-point entries as a contiguous 2 x m (k1; k2) buffer"""
+    kd = np.ascontiguousarray(np.asarray(radial, dtype=np.float64).reshape(2, -1).T)
+    if kd.shape != (m, 2):
+        raise ValueError(f"radial: expected 2 x {m} coefficients, got {np.shape(radial)}")
+    return kd
+
+
+def triangulate_points(K, Te, w, obs_ptr, obs_cam, obs_x, device=0, return_status=False,
+                       radial=None):
     """X = triangulation(P, x) (toolbox/geometry/triangulation.m:19-53) for every
     point of a batch on the GPU (vlgba_triangulate).  K (4 x m), Te, w (3 x m):
     the pinhole cameras; point i has the views obs_ptr[i] .. obs_ptr[i+1]-1 of
@@ -811,18 +863,28 @@ def triangulate_points(K, Te, w, obs_ptr, obs_cam, obs_x, device=0, return_statu
     image points).  Returns X (4 x n): the point over its 4th entry, or zeros
     when a view sees it at negative depth (status 0), when it has fewer than two
     views or the result is not finite (status 2; the reference would return
-    inf / nan for a point at infinity).  ``return_status``: (X, status)."""
+    inf / nan for a point at infinity).  ``return_status``: (X, status).
+    ``radial`` = kd (2 x m: k1; k2): the cameras have radial distortion with
+    f = K[0]; every measurement is undistorted first (vlgba_triangulate_ex), and
+    a point with a view at or past the fold of its lens gets status 2."""
     keep, args = _tracks(K, Te, w, obs_ptr, obs_cam, obs_x)
     n = args[4]
     X = np.zeros((4, n), order="F")
     status = np.zeros(n, dtype=np.int32)
-    check(lib().vlgba_triangulate(*args, int(device), _dp(X), status.ctypes.data_as(c_ip)),
-          "vlgba_triangulate")
+    if radial is None:
+        check(lib().vlgba_triangulate(*args, int(device), _dp(X), status.ctypes.data_as(c_ip)),
+              "vlgba_triangulate")
+    else:
+        kd = _radial_kd(radial, args[0])
+        check(lib().vlgba_triangulate_ex(*args[:4], _dp(kd), *args[4:], int(device), _dp(X),
+                                         status.ctypes.data_as(c_ip)), "vlgba_triangulate_ex")
     return (X, status) if return_status else X
 
 
 def bundle_euclid_intersect(K, Te, w, X, obs_ptr, obs_cam, obs_x, device=0, max_iter=0,
-                            max_iter2=0, lambda0=0.0, stop_rel=0.0, return_stats=False):
+                            max_iter2=0, lambda0=0.0, stop_rel=0.0, return_stats=False,
+                            radial=None, jacobian=None, loss="none", loss_scale=0.0,
+                            return_residuals=False):
     """Batched one-point refinement with the motion fixed --
 
         [~, ~, ~, X_i] = bundle_euclid(K, T, Omega, X_i, x_i, 'fix_calibration',
@@ -833,7 +895,14 @@ def bundle_euclid_intersect(K, Te, w, X, obs_ptr, obs_cam, obs_x, device=0, max_
     triangulate_points; X (3 or 4 x n) the start points.  Returns X_ (the same
     row count; a 4th row is passed through) and the list of per-point error_
     (SSE / views per accepted step; empty for a point without views, which is
-    left untouched)."""
+    left untouched).
+
+    Beyond the reference (vlgba_intersect_ex; with all of them at their
+    defaults the call is vlgba_intersect's, as before): ``radial`` = kd (2 x m)
+    as triangulate_points, ``jacobian``, ``loss`` / ``loss_scale`` and
+    ``return_residuals`` as bundle_euclid_resect; the residuals are one pair
+    (e (N x 2), w (N)) in the order of obs_x, appended last."""
+    ex, jac, lk, ls = _block_mode(radial, jacobian, loss, loss_scale, return_residuals)
     keep, args = _tracks(K, Te, w, obs_ptr, obs_cam, obs_x)
     n = args[4]
     X = np.asarray(X, dtype=np.float64)
@@ -846,12 +915,25 @@ def bundle_euclid_intersect(K, Te, w, X, obs_ptr, obs_cam, obs_x, device=0, max_
     opt.max_iter, opt.max_iter2, opt.lambda0 = int(max_iter), int(max_iter2), float(lambda0)
     opt.device, opt.stop_rel = int(device), float(stop_rel)
     st = VlgbaStats()
-    check(lib().vlgba_intersect(*args, ctypes.byref(opt), _dp(b), _dp(err), cap,
-                                nerr.ctypes.data_as(c_ip), ctypes.byref(st)), "vlgba_intersect")
+    if not ex:
+        check(lib().vlgba_intersect(*args, ctypes.byref(opt), _dp(b), _dp(err), cap,
+                                    nerr.ctypes.data_as(c_ip), ctypes.byref(st)),
+              "vlgba_intersect")
+    else:
+        N = len(keep[4])
+        res, wts = np.zeros((N, 2)), np.zeros(N)
+        kd = None if radial is None else _radial_kd(radial, args[0])
+        check(lib().vlgba_intersect_ex(*args[:4], None if kd is None else _dp(kd), *args[4:],
+                                       ctypes.byref(opt), jac, lk, ls, _dp(b), _dp(err), cap,
+                                       nerr.ctypes.data_as(c_ip),
+                                       _dp(res) if return_residuals else None,
+                                       _dp(wts) if return_residuals else None, ctypes.byref(st)),
+              "vlgba_intersect_ex")
     X_ = np.array(X, order="F")
     X_[:3] = b.reshape(n, 3).T
     errs = [err[q, : nerr[q]].copy() for q in range(n)]
-    return (X_, errs, st) if return_stats else (X_, errs)
+    out = (X_, errs) + ((st,) if return_stats else ())
+    return out + ((res, wts),) if return_residuals else out
 
 
 # ---------------------------------------------------------------------------

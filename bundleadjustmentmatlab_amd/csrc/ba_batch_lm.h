@@ -9,6 +9,8 @@
 // pass) into the pinned block; the pass kernel reads them with device-scope
 // vector loads and writes four doubles per problem: old SSE, new SSE,
 // dp'(lambda dp + g), pinv flag.  apply() reads those and applies :218-241.
+// Under a loss (vlgba_resect_ex, vlgba_intersect_ex) the pass reports the robust
+// cost and gradient in the same places; nothing here changes.
 //   flags: 1 active | 2 linearise again (the parameters changed) | 4 the
 //          previous pass was accepted (take x_new as x first)
 #pragma once
@@ -33,6 +35,18 @@ struct rs_pool {
 };
 int rs_acquire(int device, size_t need, rs_pool &r);   // ba_resect.hip
 void rs_release(const rs_pool &r);
+
+// the mode arguments of the _ex entries: the kinds of vlgba_set_jacobian and
+// vlgba_set_loss and the latter's scale rule; the radial model is analytic only
+inline int batch_check_mode(int jacobian, int loss, double loss_scale, bool radial)
+{
+    if (jacobian != VLGBA_JAC_FD && jacobian != VLGBA_JAC_ANALYTIC) return VLGBA_E_ARG;
+    if (radial && jacobian == VLGBA_JAC_FD) return VLGBA_E_ARG;
+    if (loss < VLGBA_LOSS_NONE || loss > VLGBA_LOSS_CAUCHY) return VLGBA_E_ARG;
+    if (loss != VLGBA_LOSS_NONE && !(std::isfinite(loss_scale) && loss_scale > 0))
+        return VLGBA_E_ARG;
+    return 0;
+}
 
 struct batch_lm {
     size_t np;

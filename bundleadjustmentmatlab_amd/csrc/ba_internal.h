@@ -73,7 +73,8 @@ struct ba_flags {
     int has_pivot;      // pivot[m] mask      (:150-154)
 };
 
-// robust loss of the fast path (vlgba_set_loss; vlg_loss in ba_kernels.hip):
+// robust loss of the fast path and the batched one-block entries
+// (vlgba_set_loss, vlgba_resect_ex; vlg_loss in vlg_math.h):
 // kind 0 none, 1 Huber, 2 Cauchy; c the scale in pixels
 struct ba_loss {
     int kind;

@@ -106,37 +106,8 @@ __device__ __forceinline__ void block_sum_to(double v, double *out)
     }
 }
 
-// -------------------------------------------------------------------------
-// Robust loss of one observation (first-order IRLS): s =
-// e0^2 + e1^2 in pixels^2, c the scale in pixels.  rho(s) is the observation's
-// cost, sqrtw = sqrt(rho'(s)) the factor of its Jacobian rows and residual.
-//   1 Huber   rho = s (s <= c^2), else 2 c sqrt(s) - c^2;  w = 1, else c / sqrt(s)
-//   2 Cauchy  rho = c^2 log1p(s / c^2);                     w = 1 / (1 + s / c^2)
-// The inlier branch of Huber returns s and 1.0 themselves: with every s below
-// c^2 a pass computes the bits of the plain one.
-// -------------------------------------------------------------------------
-__device__ __forceinline__ void vlg_loss(int kind, double c, double s, double *rho,
-                                         double *sqrtw)
-{
-    const double c2 = c * c;
-    if (kind == 1) {
-        if (s <= c2) {
-            *rho = s;
-            *sqrtw = 1.0;
-        } else {
-            const double r = sqrt(s);
-            *rho = 2.0 * c * r - c2;
-            *sqrtw = sqrt(c / r);
-        }
-    } else if (kind == 2) {
-        const double q = s / c2;
-        *rho = c2 * log1p(q);
-        *sqrtw = sqrt(1.0 / (1.0 + q));
-    } else {
-        *rho = s;
-        *sqrtw = 1.0;
-    }
-}
+// (the robust loss of one observation, vlg_loss: vlg_math.h, shared with the
+// batched one-block passes of ba_resect.hip and ba_triang.hip)
 
 // -------------------------------------------------------------------------
 // The 9 FD columns of [A | B] for fix_calibration (NA = 6), shared by the two

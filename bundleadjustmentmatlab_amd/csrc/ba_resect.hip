@@ -25,6 +25,10 @@
 // (bundle_euclid.m:205-241, glibc pow for the lambda rule) stays on the host,
 // per problem, exactly as vlgba_run applies it (ba_batch_lm.h, shared with the
 // per-point dual vlgba_intersect of ba_triang.hip).
+//
+// vlgba_resect_ex (include/vlgba.h) runs the same pass with the fused path's
+// analytic Jacobians, radial-distortion camera (num_a = 9) and robust losses:
+// further instantiations of k_resect_pass (below), the same host control.
 #include "ba_camera.h"
 #include "ba_batch_lm.h"
 #include "../../include/vlgba.h"
@@ -39,16 +43,48 @@
 
 // state per problem: U (NA x NA) | eA (NA) | old SSE, kept across rejected
 // passes (bundle_euclid.m:139 recomputes an identical linearisation, Q12)
+//
+// The modes of vlgba_resect_ex.  JAC: the closed-form camera columns of
+// cam_view<NA>::jac_columns (one evaluation per observation instead of NA + 1
+// projections) from the table R(w), dR/dw_k of rotations5_jac; the projection,
+// and with it every residual and the cost at equal parameters, is the FD
+// mode's bit for bit.  NA = BA_RAD_NA (radial lens) exists with JAC alone.
+// LOSS: the observation's row [A | e] times sqrt(w) where it is formed
+// (vlg_loss), the old / new cost sum rho(s) in observation order -- a plain
+// term (vlg_loss_plain) added as the plain pass adds it -- and the gradient of
+// dp'(lambda dp + g) the weighted eA: the rules of vlgba_set_loss.  The row then
+// carries the observation's two cost terms in two more columns, formed by its
+// own lane: the accumulator lanes' serial walk over the tile is what a pass
+// waits for, and it stays two loads and two adds per observation.
+// <NA, false, false> is vlgba_resect's pass.  LDS at the widest row (NA = 10,
+// LOSS): 256 x 25 doubles = 50 KB of At and under 3 KB of the rest.
 template <int NA>
+__device__ __forceinline__ void resect_project_new(const double *k4, const double *an,
+                                                   const double *rotn, const double b[3],
+                                                   double xh[2])
+{
+    if constexpr (NA == BA_RAD_NA) {
+        vlg_project_radial(an + 6, k4 + 2, rotn, an + 3, b, xh);
+    } else {
+        double Kc[9];
+        vlg_calib(Kc, k4, an, NA - 6);
+        vlg_project(Kc, rotn, an + 3, b, xh);
+    }
+}
+
+template <int NA, bool JAC, bool LOSS>
 __global__ __launch_bounds__(256) void k_resect_pass(
     int nprob, const long long *__restrict__ obs_ptr, const double *__restrict__ Xw,
     const double *__restrict__ xo, const double *__restrict__ K4, double *__restrict__ a,
     double *__restrict__ a_new, double *__restrict__ state, const double *__restrict__ lam_p,
-    const double *__restrict__ flags, double *__restrict__ out)
+    const double *__restrict__ flags, double *__restrict__ out, ba_loss ls)
 {
+    static_assert(JAC || NA != BA_RAD_NA, "the radial model is analytic only");
     constexpr int NUE = NA * NA + NA + 1;
+    // LOSS: two cost terms more, and a pad that keeps the row stride odd
+    constexpr int RW = 2 * NA + 2 + (LOSS ? 3 : 0);
     __shared__ double rot[45], rotn[9], k4[4], av[NA], an[NA];
-    __shared__ double At[RS_TILE][2 * NA + 2];     // A (2 x NA, column major) | e
+    __shared__ double At[RS_TILE][RW];     // A (2 x NA, column major) | e (| cost terms)
     __shared__ double st[NUE], S[NA * NA], rhs[NA], da[NA];
     __shared__ int fail;
     const int pb = blockIdx.x, tid = threadIdx.x;
@@ -70,7 +106,8 @@ __global__ __launch_bounds__(256) void k_resect_pass(
     if (fl & 2) {   // linearise at a (mex_bundle_1 for this camera)
         if (tid == 0) {
             const double w[3] = {av[0], av[1], av[2]};
-            rotations5(w, rot);
+            if constexpr (JAC) rotations5_jac(w, rot);
+            else rotations5(w, rot);
         }
         double acc = 0.0;   // lane q < NUE: U[q] | eA[q - NA^2] | old SSE
         __syncthreads();
@@ -83,15 +120,39 @@ __global__ __launch_bounds__(256) void k_resect_pass(
                 double xh[2];
                 cv.project(b, xh);
                 double *row = At[tid];
+                if constexpr (JAC) {
+                    // both halves of the closed form; its point columns (the six
+                    // entries past 2 NA) are not stored
+                    double jr[2 * NA + 6];
+                    cv.jac_columns(b, 0, jr);
+                    cv.jac_columns(b, 1, jr);
+#pragma unroll
+                    for (int k = 0; k < 2 * NA; k++) row[k] = jr[k];
+                } else {
 #pragma unroll 1
-                for (int k = 0; k < NA; k++) {   // derivative_camera (:14-41)
-                    double x1[2];
-                    cv.project_dcam(k, b, x1);
-                    row[2 * k] = vlg_fd_quot(x1[0] - xh[0]);
-                    row[2 * k + 1] = vlg_fd_quot(x1[1] - xh[1]);
+                    for (int k = 0; k < NA; k++) {   // derivative_camera (:14-41)
+                        double x1[2];
+                        cv.project_dcam(k, b, x1);
+                        row[2 * k] = vlg_fd_quot(x1[0] - xh[0]);
+                        row[2 * k + 1] = vlg_fd_quot(x1[1] - xh[1]);
+                    }
                 }
                 row[2 * NA] = xo[2 * o] - xh[0];          // e = X - X_hat (:222-223)
                 row[2 * NA + 1] = xo[2 * o + 1] - xh[1];
+                if constexpr (LOSS) {
+                    const double e0 = row[2 * NA], e1 = row[2 * NA + 1];
+                    const double s = e0 * e0 + e1 * e1;
+                    double rho, sw;
+                    vlg_loss(ls.kind, ls.c, s, &rho, &sw);
+#pragma unroll 1
+                    for (int k = 0; k < 2 * NA + 2; k++) row[k] *= sw;
+                    // the two terms the cost lane adds, so that its serial loop
+                    // stays free of branches: a plain term's e0 e0 and e1 e1, as
+                    // the plain pass adds them, else rho and an exact + 0
+                    const bool plain = vlg_loss_plain(ls.kind, ls.c, s);
+                    row[2 * NA + 2] = plain ? e0 * e0 : rho;
+                    row[2 * NA + 3] = plain ? e1 * e1 : 0.0;
+                }
             }
             __syncthreads();
             if (tid < NA * NA) {                  // U += A'A, entry (r, c) (:281-290)
@@ -104,8 +165,13 @@ __global__ __launch_bounds__(256) void k_resect_pass(
                     acc += At[q][2 * r] * At[q][2 * NA] + At[q][2 * r + 1] * At[q][2 * NA + 1];
             } else if (tid == NUE - 1) {          // e(:)'e(:) in MATLAB's flat order
                 for (int q = 0; q < nt; q++) {
-                    acc = acc + At[q][2 * NA] * At[q][2 * NA];
-                    acc = acc + At[q][2 * NA + 1] * At[q][2 * NA + 1];
+                    if constexpr (LOSS) {
+                        acc = acc + At[q][2 * NA + 2];
+                        acc = acc + At[q][2 * NA + 3];
+                    } else {
+                        acc = acc + At[q][2 * NA] * At[q][2 * NA];
+                        acc = acc + At[q][2 * NA + 1] * At[q][2 * NA + 1];
+                    }
                 }
             }
             __syncthreads();
@@ -237,17 +303,31 @@ __global__ __launch_bounds__(256) void k_resect_pass(
         if (tid < nt) {
             const long long o = o0 + t0 + tid;
             const double b[3] = {Xw[3 * o], Xw[3 * o + 1], Xw[3 * o + 2]};
-            double Kc[9], xh[2];
-            vlg_calib(Kc, k4, an, NA - 6);
-            vlg_project(Kc, rotn, an + 3, b, xh);
-            At[tid][0] = xo[2 * o] - xh[0];
-            At[tid][1] = xo[2 * o + 1] - xh[1];
+            double xh[2];
+            resect_project_new<NA>(k4, an, rotn, b, xh);
+            const double e0 = xo[2 * o] - xh[0], e1 = xo[2 * o + 1] - xh[1];
+            if constexpr (LOSS) {   // the two terms of the cost, as above
+                const double s = e0 * e0 + e1 * e1;
+                double rho, sw;
+                vlg_loss(ls.kind, ls.c, s, &rho, &sw);
+                const bool plain = vlg_loss_plain(ls.kind, ls.c, s);
+                At[tid][0] = plain ? e0 * e0 : rho;
+                At[tid][1] = plain ? e1 * e1 : 0.0;
+            } else {
+                At[tid][0] = e0;
+                At[tid][1] = e1;
+            }
         }
         __syncthreads();
         if (tid == 0)
             for (int q = 0; q < nt; q++) {
-                nsum = nsum + At[q][0] * At[q][0];
-                nsum = nsum + At[q][1] * At[q][1];
+                if constexpr (LOSS) {
+                    nsum = nsum + At[q][0];
+                    nsum = nsum + At[q][1];
+                } else {
+                    nsum = nsum + At[q][0] * At[q][0];
+                    nsum = nsum + At[q][1] * At[q][1];
+                }
             }
         __syncthreads();
     }
@@ -261,12 +341,90 @@ __global__ __launch_bounds__(256) void k_resect_pass(
     }
 }
 
+// res_out / w_out of vlgba_resect_ex: the unweighted residuals x - x_hat and the
+// loss's weights (sqrt(w) squared; 1 without a loss) at the returned parameters
+// a, one workgroup per camera; either pointer may be NULL
+template <int NA>
+__global__ __launch_bounds__(256) void k_resect_residuals(
+    int nprob, const long long *__restrict__ obs_ptr, const double *__restrict__ Xw,
+    const double *__restrict__ xo, const double *__restrict__ K4, const double *__restrict__ a,
+    ba_loss ls, double *__restrict__ res, double *__restrict__ wt)
+{
+    __shared__ double rotn[9], k4[4], av[NA];
+    const int pb = blockIdx.x, tid = threadIdx.x;
+    if (pb >= nprob) return;
+    if (tid < NA) av[tid] = a[(size_t)NA * pb + tid];
+    if (tid < 4) k4[tid] = K4[4 * (size_t)pb + tid];
+    __syncthreads();
+    if (tid == 0) {
+        const double w[3] = {av[0], av[1], av[2]};
+        vlg_rodrigues(rotn, w);
+    }
+    __syncthreads();
+    for (long long o = obs_ptr[pb] + tid; o < obs_ptr[pb + 1]; o += 256) {
+        const double b[3] = {Xw[3 * o], Xw[3 * o + 1], Xw[3 * o + 2]};
+        double xh[2], rho, sw;
+        resect_project_new<NA>(k4, av, rotn, b, xh);
+        const double e0 = xo[2 * o] - xh[0], e1 = xo[2 * o + 1] - xh[1];
+        vlg_loss(ls.kind, ls.c, e0 * e0 + e1 * e1, &rho, &sw);
+        if (res) {
+            res[2 * o] = e0;
+            res[2 * o + 1] = e1;
+        }
+        if (wt) wt[o] = sw * sw;
+    }
+}
+
 namespace {
 template <typename T>
 int dmalloc_n(T **p, size_t n)
 {
     *p = (T *)ba_dmalloc(sizeof(T) * (n ? n : 1));
     return *p ? 0 : -(int)hipErrorOutOfMemory;
+}
+
+// the pass of one mode at the runtime num_a
+struct rs_args {
+    int np;
+    const long long *ptr;
+    const double *X, *x, *K;
+    double *a, *an, *st;
+    const double *lam, *fl;
+    double *out;
+    ba_loss ls;
+};
+
+template <int NA, bool JAC, bool LOSS>
+void rs_launch_one(const rs_args &g, hipStream_t s)
+{
+    k_resect_pass<NA, JAC, LOSS><<<g.np, 256, 0, s>>>(g.np, g.ptr, g.X, g.x, g.K, g.a, g.an, g.st,
+                                                      g.lam, g.fl, g.out, g.ls);
+}
+
+// 0, or VLGBA_E_ARG for a (num_a, mode) pair that has no kernel (the radial
+// model under forward differences): nothing is launched then
+template <bool JAC, bool LOSS>
+int rs_launch_na(int na, const rs_args &g, hipStream_t s)
+{
+    switch (na) {
+    case 6: rs_launch_one<6, JAC, LOSS>(g, s); return 0;
+    case 7: rs_launch_one<7, JAC, LOSS>(g, s); return 0;
+    case 10: rs_launch_one<10, JAC, LOSS>(g, s); return 0;
+    case BA_RAD_NA:
+        if constexpr (JAC) {
+            rs_launch_one<BA_RAD_NA, true, LOSS>(g, s);
+            return 0;
+        }
+        return VLGBA_E_ARG;
+    default: return VLGBA_E_ARG;
+    }
+}
+
+int rs_launch(int na, bool jac, const rs_args &g, hipStream_t s)
+{
+    if (jac) return g.ls.kind ? rs_launch_na<true, true>(na, g, s)
+                              : rs_launch_na<true, false>(na, g, s);
+    return g.ls.kind ? rs_launch_na<false, true>(na, g, s) : rs_launch_na<false, false>(na, g, s);
 }
 std::mutex g_rs_pool_mu;
 std::vector<rs_pool> g_rs_pool;
@@ -307,14 +465,20 @@ void rs_release(const rs_pool &r)
     g_rs_pool.push_back(r);
 }
 
-extern "C" int vlgba_resect(const vlgba_resect_problem *pr, const vlgba_options *opt, double *a,
-                            double *error_out, int error_cap, int *num_error,
-                            vlgba_stats *stats)
+namespace {
+// vlgba_resect (ex false: num_a 6 / 7 / 10, forward differences, no loss) and
+// vlgba_resect_ex
+int resect_run(const vlgba_resect_problem *pr, const vlgba_options *opt, bool ex, int jacobian,
+               ba_loss ls, double *a, double *error_out, int error_cap, int *num_error,
+               double *res_out, double *w_out, vlgba_stats *stats)
 {
     if (!pr || !a || pr->nprob < 0 || !pr->obs_ptr || (error_out && error_cap < 0))
         return VLGBA_E_ARG;
     const int na = pr->num_a, np = pr->nprob;
-    if (na != 6 && na != 7 && na != 10) return VLGBA_E_NUMA;
+    if (na != 6 && na != 7 && na != 10 && !(ex && na == BA_RAD_NA)) return VLGBA_E_NUMA;
+    if (ex)
+        if (int rc = batch_check_mode(jacobian, ls.kind, ls.c, na == BA_RAD_NA)) return rc;
+    if (ls.kind == VLGBA_LOSS_NONE) ls.c = 0.0;
     if (np == 0) return 0;
     const long long N = pr->obs_ptr[np];
     if (pr->obs_ptr[0] != 0 || N < 0 || (N > 0 && (!pr->X || !pr->x)) || !pr->K)
@@ -336,7 +500,7 @@ extern "C" int vlgba_resect(const vlgba_resect_problem *pr, const vlgba_options 
     const int NUE = na * na + na + 1;
     long long *d_ptr = nullptr;
     double *d_X = nullptr, *d_x = nullptr, *d_K = nullptr, *d_a = nullptr, *d_an = nullptr;
-    double *d_st = nullptr, *d_lam = nullptr, *d_out = nullptr, *d_fl = nullptr;
+    double *d_st = nullptr, *d_lam = nullptr, *d_out = nullptr, *d_fl = nullptr, *d_res = nullptr;
     int rc = 0;
     batch_lm lm((size_t)np, opt);   // the LM control, per problem (ba_batch_lm.h)
     do {
@@ -366,20 +530,11 @@ extern "C" int vlgba_resect(const vlgba_resect_problem *pr, const vlgba_options 
                 rc = -1;
                 break;
             }
-            switch (na) {
-            case 6:
-                k_resect_pass<6><<<np, 256, 0, s>>>(np, d_ptr, d_X, d_x, d_K, d_a, d_an, d_st,
-                                                    d_lam, d_fl, d_out);
+            if ((rc = rs_launch(na, jacobian == VLGBA_JAC_ANALYTIC,
+                                rs_args{np, d_ptr, d_X, d_x, d_K, d_a, d_an, d_st, d_lam, d_fl,
+                                        d_out, ls},
+                                s)))
                 break;
-            case 7:
-                k_resect_pass<7><<<np, 256, 0, s>>>(np, d_ptr, d_X, d_x, d_K, d_a, d_an, d_st,
-                                                    d_lam, d_fl, d_out);
-                break;
-            default:
-                k_resect_pass<10><<<np, 256, 0, s>>>(np, d_ptr, d_X, d_x, d_K, d_a, d_an, d_st,
-                                                     d_lam, d_fl, d_out);
-                break;
-            }
             if (hipGetLastError() != hipSuccess ||
                 hipMemcpyAsync(h_out, d_out, sizeof(double) * 4 * np, hipMemcpyDeviceToHost,
                                s) != hipSuccess ||
@@ -404,12 +559,64 @@ extern "C" int vlgba_resect(const vlgba_resect_problem *pr, const vlgba_options 
             if (lm.accepted_prev[q])
                 std::memcpy(a + (size_t)na * q, an.data() + (size_t)na * q, sizeof(double) * na);
         lm.write_errors(error_out, error_cap, num_error);
+        if (N > 0 && (res_out || w_out)) {   // at the returned parameters
+            if ((rc = dmalloc_n(&d_res, 3 * (size_t)N))) break;
+            if (hipMemcpyAsync(d_a, a, sizeof(double) * na * np, hipMemcpyHostToDevice, s) !=
+                hipSuccess) {
+                rc = -1;
+                break;
+            }
+            double *d_w = d_res + 2 * (size_t)N;
+            switch (na) {
+            case 6:
+                k_resect_residuals<6><<<np, 256, 0, s>>>(np, d_ptr, d_X, d_x, d_K, d_a, ls, d_res,
+                                                         d_w);
+                break;
+            case 7:
+                k_resect_residuals<7><<<np, 256, 0, s>>>(np, d_ptr, d_X, d_x, d_K, d_a, ls, d_res,
+                                                         d_w);
+                break;
+            case BA_RAD_NA:
+                k_resect_residuals<BA_RAD_NA><<<np, 256, 0, s>>>(np, d_ptr, d_X, d_x, d_K, d_a, ls,
+                                                                 d_res, d_w);
+                break;
+            default:
+                k_resect_residuals<10><<<np, 256, 0, s>>>(np, d_ptr, d_X, d_x, d_K, d_a, ls, d_res,
+                                                          d_w);
+                break;
+            }
+            if (hipGetLastError() != hipSuccess ||
+                (res_out && hipMemcpyAsync(res_out, d_res, sizeof(double) * 2 * N,
+                                           hipMemcpyDeviceToHost, s) != hipSuccess) ||
+                (w_out && hipMemcpyAsync(w_out, d_w, sizeof(double) * N, hipMemcpyDeviceToHost,
+                                         s) != hipSuccess) ||
+                hipStreamSynchronize(s) != hipSuccess)
+                rc = -1;
+        }
     } while (0);
     (void)hipStreamSynchronize(s);
     for (void *p : {(void *)d_ptr, (void *)d_X, (void *)d_x, (void *)d_K, (void *)d_a,
-                    (void *)d_an, (void *)d_st, (void *)d_lam, (void *)d_out})
+                    (void *)d_an, (void *)d_st, (void *)d_lam, (void *)d_out, (void *)d_res})
         if (p) ba_dfree(p);
     rs_release(pool);
     lm.fill_stats(stats, t0);
     return rc;
+}
+}   // namespace
+
+extern "C" int vlgba_resect(const vlgba_resect_problem *pr, const vlgba_options *opt, double *a,
+                            double *error_out, int error_cap, int *num_error,
+                            vlgba_stats *stats)
+{
+    return resect_run(pr, opt, false, VLGBA_JAC_FD, ba_loss{VLGBA_LOSS_NONE, 0.0}, a, error_out,
+                      error_cap, num_error, nullptr, nullptr, stats);
+}
+
+extern "C" int vlgba_resect_ex(const vlgba_resect_problem *pr, const vlgba_options *opt,
+                               int jacobian, int loss, double loss_scale, double *a,
+                               double *error_out, int error_cap, int *num_error, double *res_out,
+                               double *w_out, vlgba_stats *stats)
+{
+    return resect_run(pr, opt, true, jacobian, ba_loss{loss, loss_scale}, a, error_out, error_cap,
+                      num_error, res_out, w_out, stats);
 }

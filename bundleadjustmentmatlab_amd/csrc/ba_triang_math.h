@@ -7,6 +7,9 @@
  * Camera records (k_tri_cameras writes them once per call):
  *   TRI_CAM doubles per camera:  P (12, 3 x 4 column major:
  *   calibration_matrix(K) [R(w) T]) | K4 (4) | R(w) (9) | T (3)
+ * Radial lenses (vlgba_triangulate_ex, vlgba_intersect_ex): the record is the
+ * pinhole one with K4 = (f, f, cx, cy); k1, k2 travel in a side array kd (2 per
+ * camera), so the pinhole record and its arithmetic stay what they were.
  */
 #ifndef BA_TRIANG_MATH_H
 #define BA_TRIANG_MATH_H
@@ -150,16 +153,94 @@ VLG_HD void tri_smallest_vec(const double G[10], double v[4])
 /* point of nv views (camera ids cam[], measurements x[2 * .]) from the camera
  * records: X (4) and the status 1 triangulated / 0 behind a camera / 2 fewer
  * than two views or a non-finite result (X zeros unless 1) */
+VLG_HD int tri_solve(const double G[10], long long nv, const int *cam, const double *rec,
+                     double X[4]);
+
 VLG_HD int tri_point(long long nv, const int *cam, const double *x, const double *rec, double X[4])
 {
-    double G[10], v[4];
+    double G[10];
     long long o;
-    int c, st = 1;
+    int c;
     X[0] = X[1] = X[2] = X[3] = 0.0;
     if (nv < 2) return 2;
     for (c = 0; c < 10; c++) G[c] = 0.0;
     for (o = 0; o < nv; o++)
         tri_add_view(G, rec + (size_t)TRI_CAM * cam[o], x[2 * o], x[2 * o + 1]);
+    return tri_solve(G, nv, cam, rec, X);
+}
+
+/* Undistortion of one measurement x under the radial lens (f, k1, k2,
+ * principal point c): nd = (x - c) / f, rd = |nd|; solve r (1 + k1 r^2 +
+ * k2 r^4) = rd by Newton from r = rd, then n = nd (r / rd), n = 0 at rd = 0.
+ * At most TRI_UNDIST_ITERS updates; settled when an update changes r by no
+ * more than TRI_UNDIST_TOL |r| (8 ulps: the residual r g(r) - rd is itself
+ * only good to a few ulps of rd, so a smaller update is rounding).  Returns 0
+ * (the view fails) when the derivative 1 + 3 k1 r^2 + 5 k2 r^4 is <= 0 at any
+ * iterate or at the settled r (at or past the fold of the lens, where the
+ * distortion stops being invertible), when the iteration does not settle, and
+ * for a non-finite result; 1 otherwise. */
+#define TRI_UNDIST_ITERS 20
+#define TRI_UNDIST_TOL 0x1p-49
+VLG_HD int tri_undistort(double f, const double c[2], double k1, double k2, const double x[2],
+                         double n[2])
+{
+    const double nd0 = (x[0] - c[0]) / f, nd1 = (x[1] - c[1]) / f;
+    const double rd = sqrt(nd0 * nd0 + nd1 * nd1);
+    double r = rd, r2, dg;
+    int it, ok = 0;
+    n[0] = n[1] = 0.0;
+    if (rd == 0.0) return 1;
+    for (it = 0; it < TRI_UNDIST_ITERS && !ok; it++) {
+        double g, dr;
+        r2 = r * r;
+        g = (1.0 + k1 * r2) + (k2 * r2) * r2;
+        dg = (1.0 + 3.0 * (k1 * r2)) + 5.0 * ((k2 * r2) * r2);
+        if (!(dg > 0.0)) return 0;
+        dr = (r * g - rd) / dg;
+        r = r - dr;
+        ok = fabs(dr) <= TRI_UNDIST_TOL * fabs(r);
+    }
+    r2 = r * r;
+    dg = (1.0 + 3.0 * (k1 * r2)) + 5.0 * ((k2 * r2) * r2);
+    if (!ok || !(dg > 0.0) || !(r > 0.0) || !(r <= 1.79769313486231570e308)) return 0;
+    n[0] = nd0 * (r / rd);
+    n[1] = nd1 * (r / rd);
+    return 1;
+}
+
+/* tri_point under radial lenses (kd: k1, k2 per camera; f = K4[0], the
+ * principal point K4[2], K4[3] of the record, whose P was formed with K =
+ * (f, f, cx, cy)): every measurement is undistorted to the pinhole pixel
+ * f n + c first, then the rows are tri_point's.  A view that tri_undistort
+ * fails gives the point status 2 and zeros. */
+VLG_HD int tri_point_radial(long long nv, const int *cam, const double *x, const double *rec,
+                            const double *kd, double X[4])
+{
+    double G[10];
+    long long o;
+    int c;
+    X[0] = X[1] = X[2] = X[3] = 0.0;
+    if (nv < 2) return 2;
+    for (c = 0; c < 10; c++) G[c] = 0.0;
+    for (o = 0; o < nv; o++) {
+        const double *rc = rec + (size_t)TRI_CAM * cam[o];
+        const double *k4 = rc + TRI_CAM_K4;
+        double n[2];
+        if (!tri_undistort(k4[0], k4 + 2, kd[2 * (size_t)cam[o]], kd[2 * (size_t)cam[o] + 1],
+                           x + 2 * o, n))
+            return 2;
+        tri_add_view(G, rc, k4[0] * n[0] + k4[2], k4[0] * n[1] + k4[3]);
+    }
+    return tri_solve(G, nv, cam, rec, X);
+}
+
+/* the point from the Gram matrix of its rows: X (zeros unless status 1) */
+VLG_HD int tri_solve(const double G[10], long long nv, const int *cam, const double *rec,
+                     double X[4])
+{
+    double v[4];
+    long long o;
+    int st = 1;
     tri_smallest_vec(G, v);
     {
         const double x0 = v[0] / v[3], x1 = v[1] / v[3], x2 = v[2] / v[3];
@@ -190,42 +271,133 @@ VLG_HD void isect_project(const double *rc, const double b[3], double x[2])
     vlg_project(Kc, rc + TRI_CAM_R, rc + TRI_CAM_T, b, x);
 }
 
+/* The mode of vlgba_intersect_ex.  kd: NULL pinhole, else k1, k2 per camera
+ * (radial lens, f = K4[0], principal point K4[2], K4[3]: vlg_project_radial);
+ * jac: 0 forward differences, 1 the closed-form B; loss / c: vlg_loss.  The
+ * pass is a template over M: M = false is vlgba_intersect's (the mode is not
+ * read, every branch on it folds away); M = true with kd NULL, jac 0, loss 0
+ * performs the same operations in the same order. */
+typedef struct {
+    const double *kd;
+    int jac, loss;
+    double c;
+} isect_mode;
+
+VLG_HD void isect_project_m(const double *rc, const double *k12, const double b[3], double x[2])
+{
+    if (k12) {
+        const double k[3] = {rc[TRI_CAM_K4], k12[0], k12[1]};
+        vlg_project_radial(k, rc + TRI_CAM_K4 + 2, rc + TRI_CAM_R, rc + TRI_CAM_T, b, x);
+    } else {
+        isect_project(rc, b, x);
+    }
+}
+
+/* B = dx/db in closed form (column k at B[2k], B[2k+1]): the B columns of
+ * cam_view<6>::jac_columns and cam_view<BA_RAD_NA>::jac_columns (ba_camera.h)
+ * restated for host and device, operation for operation */
+VLG_HD void isect_jac_B(const double *rc, const double *k12, const double b[3], double B[6])
+{
+    const double *R = rc + TRI_CAM_R, *T = rc + TRI_CAM_T;
+    int k;
+    if (k12) {
+        const double kk[3] = {rc[TRI_CAM_K4], k12[0], k12[1]};
+        double n[2], iz, r2, d;
+        vlg_radial_n(kk, R, T, b, n, &iz, &r2, &d);
+        {
+            const double f = kk[0], u = n[0], v = n[1];
+            const double g = 2.0 * kk[1] + 4.0 * (kk[2] * r2);
+            const double fd = f * d, fgu = (f * g) * u, fgv = (f * g) * v;
+            for (k = 0; k < 3; k++) {
+                const double p0 = iz * (R[3 * k] - u * R[3 * k + 2]);
+                const double p1 = iz * (R[3 * k + 1] - v * R[3 * k + 2]);
+                const double s = u * p0 + v * p1;
+                B[2 * k] = fd * p0 + fgu * s;
+                B[2 * k + 1] = fd * p1 + fgv * s;
+            }
+        }
+    } else {
+        double S[3];
+        vlg_rot_b(R, b, S);
+        {
+            const double X0 = S[0] + T[0], X1 = S[1] + T[1], z = S[2] + T[2];
+            const double iz = 1.0 / z;
+            const double u = X0 * iz, v = X1 * iz;
+            const double fxz = rc[TRI_CAM_K4] * iz, fyz = rc[TRI_CAM_K4 + 1] * iz;
+            for (k = 0; k < 3; k++) {
+                B[2 * k] = fxz * (R[3 * k] - u * R[3 * k + 2]);
+                B[2 * k + 1] = fyz * (R[3 * k + 1] - v * R[3 * k + 2]);
+            }
+        }
+    }
+}
+
+/* one residual's term of the (robust) cost, added as the plain pass adds it
+ * when it is the plain term (vlg_loss_plain) */
+template <bool M>
+VLG_HD double isect_cost_add(double acc, const isect_mode *md, double e0, double e1)
+{
+    const double s = e0 * e0 + e1 * e1;
+    if (!M || vlg_loss_plain(md->loss, md->c, s)) {
+        acc = acc + e0 * e0;
+        acc = acc + e1 * e1;
+    } else {
+        double rho, sw;
+        vlg_loss(md->loss, md->c, s, &rho, &sw);
+        acc = acc + rho;
+    }
+    return acc;
+}
+
 /* linearise at b (mex_bundle_1_XABeUVWeAeB.c:43-70, 196-225, 280-332 for this
  * point's columns): V = sum B'B, eB = sum B'e and e(:)'e(:) in view order */
+template <bool M>
 VLG_HD void isect_linearize(long long nv, const int *cam, const double *x, const double *rec,
-                            const double b[3], double st[TRI_NST])
+                            const isect_mode *md, const double b[3], double st[TRI_NST])
 {
     long long o;
     int r, c, k;
     for (k = 0; k < TRI_NST; k++) st[k] = 0.0;
     for (o = 0; o < nv; o++) {
         const double *rc = rec + (size_t)TRI_CAM * cam[o];
-        double xh[2], B[6], e[2];
-        isect_project(rc, b, xh);
-        for (k = 0; k < 3; k++) {
-            double b1[3], x1[2];
-            for (c = 0; c < 3; c++) b1[c] = b[c] + VLG_FD_H * ((c == k) ? 1.0 : 0.0);
-            isect_project(rc, b1, x1);
-            B[2 * k] = vlg_fd_quot(x1[0] - xh[0]);
-            B[2 * k + 1] = vlg_fd_quot(x1[1] - xh[1]);
+        const double *k12 = M && md->kd ? md->kd + 2 * (size_t)cam[o] : 0;
+        double xh[2], B[6], e[2], u[2];
+        isect_project_m(rc, k12, b, xh);
+        if (M && md->jac) {
+            isect_jac_B(rc, k12, b, B);
+        } else {
+            for (k = 0; k < 3; k++) {
+                double b1[3], x1[2];
+                for (c = 0; c < 3; c++) b1[c] = b[c] + VLG_FD_H * ((c == k) ? 1.0 : 0.0);
+                isect_project_m(rc, k12, b1, x1);
+                B[2 * k] = vlg_fd_quot(x1[0] - xh[0]);
+                B[2 * k + 1] = vlg_fd_quot(x1[1] - xh[1]);
+            }
         }
-        e[0] = x[2 * o] - xh[0];
-        e[1] = x[2 * o + 1] - xh[1];
+        u[0] = e[0] = x[2 * o] - xh[0];
+        u[1] = e[1] = x[2 * o + 1] - xh[1];
+        if (M && md->loss) {   /* the rows [B | e] times sqrt(w), where they are formed */
+            double rho, sw;
+            vlg_loss(md->loss, md->c, e[0] * e[0] + e[1] * e[1], &rho, &sw);
+            for (k = 0; k < 6; k++) B[k] *= sw;
+            e[0] *= sw;
+            e[1] *= sw;
+        }
         for (c = 0; c < 3; c++)
             for (r = 0; r < 3; r++)
                 st[r + 3 * c] += B[2 * r] * B[2 * c] + B[2 * r + 1] * B[2 * c + 1];
         for (r = 0; r < 3; r++) st[9 + r] += B[2 * r] * e[0] + B[2 * r + 1] * e[1];
-        st[12] = st[12] + e[0] * e[0];
-        st[12] = st[12] + e[1] * e[1];
+        st[12] = isect_cost_add<M>(st[12], md, u[0], u[1]);
     }
 }
 
 /* the step from the kept linearisation: V* (bundle_euclid.m:162-173), db =
  * V*^-1 eB (fix_motion: da = 0, so mex_bundle_3_db_new.c:99-134 subtracts exact
- * zeros), b_new = b + db, the new projections' e'e and dp'(lambda dp + g) */
+ * zeros), b_new = b + db, the new projections' cost and dp'(lambda dp + g) */
+template <bool M>
 VLG_HD void isect_step(long long nv, const int *cam, const double *x, const double *rec,
-                       const double b[3], const double st[TRI_NST], double lambda,
-                       double bn[3], double *new_sse, double *dpg)
+                       const isect_mode *md, const double b[3], const double st[TRI_NST],
+                       double lambda, double bn[3], double *new_cost, double *dpg)
 {
     double Vs[9], Vi[9], db[3], ns = 0.0, g = 0.0;
     long long o;
@@ -237,16 +409,35 @@ VLG_HD void isect_step(long long nv, const int *cam, const double *x, const doub
         db[r] = Vi[r] * st[9] + Vi[r + 3] * st[10] + Vi[r + 6] * st[11];
     for (r = 0; r < 3; r++) bn[r] = b[r] + db[r];
     for (o = 0; o < nv; o++) {
-        double xh[2], d0, d1;
-        isect_project(rec + (size_t)TRI_CAM * cam[o], bn, xh);
-        d0 = x[2 * o] - xh[0];
-        d1 = x[2 * o + 1] - xh[1];
-        ns = ns + d0 * d0;
-        ns = ns + d1 * d1;
+        double xh[2];
+        isect_project_m(rec + (size_t)TRI_CAM * cam[o],
+                        M && md->kd ? md->kd + 2 * (size_t)cam[o] : 0, bn, xh);
+        ns = isect_cost_add<M>(ns, md, x[2 * o] - xh[0], x[2 * o + 1] - xh[1]);
     }
     for (r = 0; r < 3; r++) g = g + db[r] * (lambda * db[r] + st[9 + r]);
-    *new_sse = ns;
+    *new_cost = ns;
     *dpg = g;
+}
+
+/* the unweighted residuals x - x_hat (2 per view) and the loss's weights (1 per
+ * view; sqrt(w) squared, 1 without a loss) of one point at b; either may be 0 */
+VLG_HD void isect_residuals_m(long long nv, const int *cam, const double *x, const double *rec,
+                              const isect_mode *md, const double b[3], double *res, double *w)
+{
+    long long o;
+    for (o = 0; o < nv; o++) {
+        double xh[2], e0, e1, rho, sw;
+        isect_project_m(rec + (size_t)TRI_CAM * cam[o],
+                        md->kd ? md->kd + 2 * (size_t)cam[o] : 0, b, xh);
+        e0 = x[2 * o] - xh[0];
+        e1 = x[2 * o + 1] - xh[1];
+        vlg_loss(md->loss, md->c, e0 * e0 + e1 * e1, &rho, &sw);
+        if (res) {
+            res[2 * o] = e0;
+            res[2 * o + 1] = e1;
+        }
+        if (w) w[o] = sw * sw;
+    }
 }
 
 #endif /* BA_TRIANG_MATH_H */

@@ -28,6 +28,7 @@
  *                           reference)
  *   vlg_drodrigues          dR/dw_k of the exponential map (analytic-Jacobian
  *                           mode; not part of the reference)
+ *   vlg_loss                robust loss of one observation (Huber, Cauchy)
  *   vlg_fd_quot             (x1 - x0) / h without a division, bit-identical
  *   vlg_pinv3               3x3 pseudo-inverse of the damped point blocks
  *
@@ -258,6 +259,45 @@ VLG_HD void vlg_project_radial(const double k[3], const double c[2], const doubl
     vlg_radial_n(k, R, t, b, n, &iz, &r2, &d);
     x[0] = k[0] * (d * n[0]) + c[0];
     x[1] = k[0] * (d * n[1]) + c[1];
+}
+
+/* ---- robust loss of one observation (first-order IRLS) ----
+ * s = e0^2 + e1^2 in pixels^2, c the scale in pixels.  rho(s) is the
+ * observation's cost, sqrtw = sqrt(rho'(s)) the factor of its Jacobian rows and
+ * residual.
+ *   1 Huber   rho = s (s <= c^2), else 2 c sqrt(s) - c^2;  w = 1, else c / sqrt(s)
+ *   2 Cauchy  rho = c^2 log1p(s / c^2);                     w = 1 / (1 + s / c^2)
+ * The inlier branch of Huber returns s and 1.0 themselves: with every s below
+ * c^2 a pass computes the bits of the plain one.                               */
+VLG_HD void vlg_loss(int kind, double c, double s, double *rho, double *sqrtw)
+{
+    const double c2 = c * c;
+    if (kind == 1) {
+        if (s <= c2) {
+            *rho = s;
+            *sqrtw = 1.0;
+        } else {
+            const double r = sqrt(s);
+            *rho = 2.0 * c * r - c2;
+            *sqrtw = sqrt(c / r);
+        }
+    } else if (kind == 2) {
+        const double q = s / c2;
+        *rho = c2 * log1p(q);
+        *sqrtw = sqrt(1.0 / (1.0 + q));
+    } else {
+        *rho = s;
+        *sqrtw = 1.0;
+    }
+}
+
+/* the observation's cost is the plain term s = e0 e0 + e1 e1 itself (no loss, a
+ * Huber inlier): the batched one-block passes, whose plain cost adds e0 e0 and
+ * e1 e1 one after the other (MATLAB's flat e(:)'e(:)), add such a term that way
+ * under a loss too, so Huber with every s below c^2 keeps the plain bits */
+VLG_HD int vlg_loss_plain(int kind, double c, double s)
+{
+    return kind == 1 ? s <= c * c : kind != 2;
 }
 
 /* Finite-difference step of the reference (mex_bundle_1_XABeUVWeAeB.c:23,52). */

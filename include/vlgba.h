@@ -46,7 +46,9 @@ extern "C" {
  * vlgba_debug_selinv_plan, VLGBA_COV_*: likewise), and the radial-distortion
  * camera num_a = 9 (a value vlgba_create refused before: no struct, constant or
  * entry point changed) and the batched per-point entries (vlgba_triangulate,
- * vlgba_intersect: entry points only).  Callers
+ * vlgba_intersect: entry points only) and their counterparts with a model, a
+ * Jacobian mode and a loss (vlgba_resect_ex, vlgba_intersect_ex,
+ * vlgba_triangulate_ex: likewise).  Callers
  * check it once at load time with VLGBA_ABI_CHECK() (the MEX gateways and the Python
  * loader do): the library compares the version and the struct sizes the
  * caller was compiled with against its own and returns 0 or VLGBA_E_ABI. */
@@ -81,9 +83,10 @@ extern "C" {
  * returns VLGBA_E_ARG for vlgba_options.ordered != 0 and for a problem that the
  * planner would hand to the ordered kernels (vlgba_plan_info [15]).  Robust
  * losses, covariances (both methods), the fix masks, every reduced solve and
- * sharded contexts work as for the other models.  Not covered (VLGBA_E_NUMA):
- * vlgba_resect, the vlgba_mex_bundle_* stage entries, the MATLAB drop-ins and
- * the GPU scene generator.
+ * sharded contexts work as for the other models; vlgba_resect_ex,
+ * vlgba_intersect_ex and vlgba_triangulate_ex take the model too.  Not covered
+ * (VLGBA_E_NUMA): vlgba_resect, the vlgba_mex_bundle_* stage entries, the MATLAB
+ * drop-ins and the GPU scene generator.
  * ------------------------------------------------------------------------ */
 typedef struct {
     int m;                 /* cameras                                            */
@@ -371,9 +374,10 @@ int vlgba_get_covariance_blocks(vlgba_ctx *ctx, int *blk_jk, double *blocks);
  * mode (vlgba_options.ordered != 0), whose purpose is bit parity with a
  * reference that has no loss.  Marks the linearisation stale: the next pass or
  * getter linearises again.  VLGBA_LOSS_NONE restores the plain solver exactly.
- * Not covered (they stay plain least squares): vlgba_resect, the
- * vlgba_mex_bundle_* stage entries and the MATLAB drop-ins, which keep the
- * reference's option list. */
+ * Not covered (they stay plain least squares): vlgba_resect and vlgba_intersect
+ * (vlgba_resect_ex and vlgba_intersect_ex take a loss), the vlgba_mex_bundle_*
+ * stage entries and the MATLAB drop-ins, which keep the reference's option
+ * list. */
 #define VLGBA_LOSS_NONE 0
 #define VLGBA_LOSS_HUBER 1
 #define VLGBA_LOSS_CAUCHY 2
@@ -403,8 +407,9 @@ int vlgba_get_loss(vlgba_ctx *ctx, int *kind, double *scale);
  * VLGBA_JAC_FD (vlgba_get_jacobian tells).  The radial-distortion camera
  * (num_a = 9) has the analytic mode only: VLGBA_JAC_FD is VLGBA_E_ARG there, and
  * the environment variable has no effect on it.  Not covered (forward differences always): ordered /
- * parity mode, vlgba_resect, the vlgba_mex_bundle_* stage entries and the
- * MATLAB drop-ins. */
+ * parity mode, vlgba_resect and vlgba_intersect (vlgba_resect_ex and
+ * vlgba_intersect_ex take the mode), the vlgba_mex_bundle_* stage entries and
+ * the MATLAB drop-ins. */
 #define VLGBA_JAC_FD 0
 #define VLGBA_JAC_ANALYTIC 1
 int vlgba_set_jacobian(vlgba_ctx *ctx, int kind);
@@ -527,7 +532,8 @@ int vlgba_mex_bundle_proj_3(int m, int n, const double *W, const double *da, con
  * num_vis = its observation count. */
 typedef struct {
     int nprob;
-    int num_a;                 /* 6 fix_calibration, 7 fix_principal, 10 free K */
+    int num_a;                 /* 6 fix_calibration, 7 fix_principal, 10 free K;
+                                  vlgba_resect_ex alone: 9 radial distortion    */
     const long long *obs_ptr;  /* [nprob + 1], obs_ptr[0] = 0                  */
     const double *X;           /* [3 * N] world point of each observation      */
     const double *x;           /* [2 * N] measured (u, v)                       */
@@ -549,8 +555,9 @@ int vlgba_resect(const vlgba_resect_problem *prob, const vlgba_options *opt, dou
  * VLGBA_E_ARG, before any device work, for a NULL pointer, m < 1, n < 0, a
  * non-monotone obs_ptr and a camera id outside [0, m); n == 0 succeeds without
  * a launch.  Host pointers in and out; thread-safe (a stream per call).
- * Not covered: the projective and radial models, robust losses, analytic
- * Jacobians, several GPUs, the MATLAB drop-ins. */
+ * Not covered by these two entries: the radial model, robust losses, analytic
+ * Jacobians (vlgba_intersect_ex and vlgba_triangulate_ex below take them); by
+ * none: the projective model, several GPUs, the MATLAB drop-ins. */
 
 /* X = triangulation(P, x) for every point (replaces toolbox/geometry/
  * triangulation.m:19-53): P_j = calibration_matrix(K_j) [R(w_j) T_j], the rows
@@ -586,6 +593,78 @@ int vlgba_intersect(int m, const double *K, const double *T, const double *w,
                     double *X /* 3 x n, start point in, result out */,
                     double *error_out, int error_cap, int *num_error,
                     vlgba_stats *stats);
+
+/* ---- the batched entries with a camera model, a Jacobian mode and a loss -----
+ * vlgba_resect, vlgba_intersect and vlgba_triangulate with the capabilities of
+ * the fused LM path; those three keep their signatures, refusals and bits.
+ *
+ * Model.  vlgba_resect_ex accepts prob->num_a 6, 7, 10 and 9 (VLGBA_E_NUMA
+ * otherwise).  At 9 the camera has radial distortion exactly as on the fused
+ * path: a = [w; T; f; k1; k2], (cx, cy) = K[2], K[3] fixed, K[0], K[1] unused.
+ * For the per-point entries a non-NULL kd (2 x m: k1; k2 per camera) makes every
+ * camera radial with f = K[0] (K[1] ignored) and (cx, cy) = K[2], K[3]; kd ==
+ * NULL is the pinhole model of vlgba_intersect / vlgba_triangulate.  The radial
+ * model is analytic only: jacobian == VLGBA_JAC_FD with num_a == 9 or kd != NULL
+ * returns VLGBA_E_ARG.
+ *
+ * Jacobians.  VLGBA_JAC_FD: the reference's forward differences.
+ * VLGBA_JAC_ANALYTIC: the closed-form columns of the fused path's analytic mode
+ * (the camera columns for resect, B = J R for intersect), for |w| < 1e-6 the
+ * limit generators [e_k]x -- a camera handed over at w = 0 rotates, which under
+ * forward differences it never does.  The projection is the same in both modes:
+ * the residuals, and so the cost at equal parameters, are the same bits.
+ * VLGBA_E_ARG for an unknown kind.
+ *
+ * Loss.  The rules of vlgba_set_loss: w = rho'(s) per observation, its Jacobian
+ * rows and residual times sqrt(w) where they are formed, the LM scalars (old /
+ * new / dp'(lambda dp + g)) the robust cost and gradient, error_ = cost / views.
+ * An observation whose cost is the plain term s itself (no loss; Huber with s <=
+ * c^2) is added as the plain pass adds it, so Huber at a scale above every
+ * residual gives the bits of VLGBA_LOSS_NONE.  VLGBA_E_ARG for an unknown kind
+ * and for a non-finite or <= 0 loss_scale when loss != VLGBA_LOSS_NONE.
+ *
+ * res_out (2 x N), w_out (N), either may be NULL: the unweighted residuals x -
+ * x_hat and the loss's weights (no loss: 1) at the RETURNED parameters, in the
+ * caller's observation order (computed once after the last pass).
+ *
+ * Summation order is that of the plain entries: observations ascending for
+ * resect, the views in the given order for intersect, sequentially.  Problem q
+ * gives the same bits alone as inside any batch, and two calls the same bits.
+ * With VLGBA_JAC_FD, VLGBA_LOSS_NONE and the pinhole model every result equals
+ * the plain entry's bit for bit.
+ *
+ * Not covered: the projective model, the MEX gateways and MATLAB drop-ins,
+ * several GPUs, the growing-reconstruction driver (incremental_bundle). */
+int vlgba_resect_ex(const vlgba_resect_problem *prob, const vlgba_options *opt,
+                    int jacobian /* VLGBA_JAC_* */, int loss /* VLGBA_LOSS_* */,
+                    double loss_scale /* pixels */, double *a,
+                    double *error_out, int error_cap, int *num_error,
+                    double *res_out /* 2 x N or NULL */, double *w_out /* N or NULL */,
+                    vlgba_stats *stats);
+
+int vlgba_intersect_ex(int m, const double *K, const double *T, const double *w,
+                       const double *kd /* 2 x m (k1; k2) or NULL: pinhole */,
+                       long long n, const long long *obs_ptr, const int *obs_cam,
+                       const double *obs_x, const vlgba_options *opt,
+                       int jacobian, int loss, double loss_scale, double *X,
+                       double *error_out, int error_cap, int *num_error,
+                       double *res_out, double *w_out, vlgba_stats *stats);
+
+/* vlgba_triangulate under radial lenses.  kd == NULL: vlgba_triangulate itself.
+ * Else every measurement x is first undistorted: nd = (x - c) / f, rd = |nd|,
+ * r (1 + k1 r^2 + k2 r^4) = rd solved by Newton from r = rd -- at most 20
+ * updates, settled when an update changes r by no more than 8 ulps (2^-49 |r|)
+ * -- and n = nd (r / rd), n = 0 at rd = 0; then triangulation.m's rows are
+ * formed from the pinhole pixel f n + c exactly as vlgba_triangulate forms them,
+ * with K = (f, f, cx, cy).  A view fails when the iteration does not settle or
+ * when 1 + 3 k1 r^2 + 5 k2 r^4 <= 0 at an iterate or at the settled r (at or
+ * past the fold of the lens); a point with such a view gets status 2 and zeros.
+ * (A lens whose k2 turns the distortion upwards again beyond the fold has a far
+ * branch; an iteration thrown onto it is not detected.) */
+int vlgba_triangulate_ex(int m, const double *K, const double *T, const double *w,
+                         const double *kd /* 2 x m or NULL */, long long n,
+                         const long long *obs_ptr, const int *obs_cam,
+                         const double *obs_x, int device, double *X, int *status);
 
 /* Multi-GPU: rank 0 creates the 128-byte RCCL unique id, the caller
  * broadcasts it (e.g. torch.distributed) and passes it as opt->comm_id.
