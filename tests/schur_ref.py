@@ -8,7 +8,8 @@ per-entry rounding bound for an fp64 evaluation of the same stage, so a stage
 is judged alone and entry by entry:
 
     schur       S_jk = U*_j [j == k] - sum_i Y_ij W_ik^T,  e_j = eA_j - sum_i Y_ij eB_i
-    residual    componentwise backward error of S da = e_
+    residual    componentwise backward error of S da = e_ (residual_blocks: the
+                same from the blocks, without the dense S)
     back_subst  db_i = V*^-1_i (eB_i - sum_j W_ij^T da_j[:ndb])
 
 The bounds count roundings and multiply by the sum of absolute values of the
@@ -219,6 +220,64 @@ def residual(S_lower_dense, e_, da, rows=None):
         return 0.0
     r = np.where(den > 0, num / np.where(den > 0, den, 1), np.where(num > 0, np.inf, 0))
     return float(r.max())
+
+
+def residual_blocks(m, na, jk, blocks, e_, da, rows=None):
+    """residual() without the dense S: the same Oettli-Prager quantity from the
+    getter's blocks (jk (nb, 2) camera pairs j >= k, each once; blocks
+    (nb, na, na) [b, r, c]; only the lower triangle of a diagonal block is
+    read and mirrored, an off-diagonal block also acts transposed on rows k),
+    numerator and denominator accumulated block by block in long double, the
+    same 0 / 0 rule, ``rows`` a bool mask over the na * m rows.
+
+    The sums are the dense product's terms in another order (a row's terms
+    inside a block first, then the blocks in jk's order; the dense product
+    adds a row's zeros too, exactly), so the two values agree to the rounding
+    of the sums and not to the last bit: residual_slack() bounds the
+    difference."""
+    jk = np.asarray(jk, dtype=np.int64).reshape(-1, 2)
+    B = np.asarray(blocks, dtype=np.float64).reshape(-1, na, na).astype(LD)
+    assert len(B) == len(jk), "one block per index pair"
+    assert np.all(jk[:, 0] >= jk[:, 1]) and np.all(jk >= 0) and np.all(jk < m), "block index"
+    key = jk[:, 0] * m + jk[:, 1]
+    assert len(np.unique(key)) == len(key), "a block returned twice"
+    e = np.asarray(e_, dtype=np.float64).reshape(-1).astype(LD)
+    x = np.asarray(da, dtype=np.float64).reshape(-1, order="F").astype(LD)
+    assert e.size == na * m and x.size == na * m
+    xc, xa = x.reshape(m, na), np.abs(x).reshape(m, na)
+    sx = np.zeros((m, na), dtype=LD)       # S x
+    ax = np.zeros((m, na), dtype=LD)       # |S| |x|
+    dg = jk[:, 0] == jk[:, 1]
+    D = np.tril(B[dg]) + np.tril(B[dg], -1).transpose(0, 2, 1)
+    j = jk[dg, 0]
+    np.add.at(sx, j, np.einsum("brc,bc->br", D, xc[j]))
+    np.add.at(ax, j, np.einsum("brc,bc->br", np.abs(D), xa[j]))
+    O, j, k = B[~dg], jk[~dg, 0], jk[~dg, 1]
+    np.add.at(sx, j, np.einsum("brc,bc->br", O, xc[k]))
+    np.add.at(ax, j, np.einsum("brc,bc->br", np.abs(O), xa[k]))
+    np.add.at(sx, k, np.einsum("brc,br->bc", O, xc[j]))
+    np.add.at(ax, k, np.einsum("brc,br->bc", np.abs(O), xa[j]))
+    num = np.abs(sx.reshape(-1) - e)
+    den = ax.reshape(-1) + np.abs(e)
+    if rows is not None:
+        num, den = num[rows], den[rows]
+    if num.size == 0:
+        return 0.0
+    r = np.where(den > 0, num / np.where(den > 0, den, 1), np.where(num > 0, np.inf, 0))
+    return float(r.max())
+
+
+def residual_slack(terms, eta=0.0):
+    """How far residual() and residual_blocks() of the same system can lie
+    apart, ``terms`` the most non-zero entries of a row of the symmetrised S.
+    Each computed row sum of t terms is within gamma = t * eps of the exact one
+    relative to sum |terms| <= den in any order (eps = 2^-64, the long double's
+    unit roundoff), so the two numerators differ by at most 2 (t + 1) eps den
+    (e_'s subtraction included), the two denominators by 2 t eps den, the
+    quotients by (2 (t + 1) + 2 t eta) eps plus the division's rounding; the
+    conversion of each result to fp64 adds 2^-53 eta.  Rounded up:
+    3 (t + 2) eps + 2^-51 eta."""
+    return 3.0 * (terms + 2) * 2.0 ** -64 + 2.0 ** -51 * eta
 
 
 def back_subst(na, ndb, pt, cam, W, Vinv, eB, da):

@@ -282,7 +282,10 @@ def _one_pass(gpu, sc, num_a, **kw):
 def test_cyclic_reduction_matches_envelope(gpu, num_a, m):
     """Banded co-visibility (tile-tridiagonal S): the default solver runs block
     cyclic reduction (log2 levels) and agrees with the sequential envelope
-    Cholesky to rounding; odd / even / power-of-two tile counts."""
+    Cholesky to rounding; odd / even / power-of-two tile counts.  (Two pass
+    scalars only: tests/test_gpu_cr_branches.py holds every entry of da on
+    this route -- the 64-row reduction at num_a 6 / 7 / 9 / 10 / 12, split and
+    unsplit bodies -- to the long double solve reference.)"""
     from bundleadjustmentmatlab_amd.scene import make_config
     sc = make_config("cfg2", m=m, n=60 * m, seed=31)
     cr, kcr = _one_pass(gpu, sc, num_a)

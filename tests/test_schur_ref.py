@@ -7,7 +7,10 @@ CPU before it judges a kernel (tests/test_gpu_stage_ref.py):
   the damping or in db leaves them;
 * the componentwise backward error separates a right solve (LAPACK Cholesky,
   the oracle's fixed-row Cholesky: well below ld * u) from a solve of a system
-  with one 6 x 6 block missing (above 1e3 * ld * u).
+  with one 6 x 6 block missing (above 1e3 * ld * u);
+* the blockwise residual (residual_blocks: no dense S) is the dense one to the
+  rounding of its long double sums, and one entry of an exact solution off by
+  a relative 1e-12 lifts it above ld * u.
 """
 import functools
 
@@ -235,6 +238,112 @@ def test_residual_rows_and_exact_zeros():
     assert sr.residual(S, [2.0, 0.0, 4.0], [1.0, 0.0, 2.0]) > 0.1
     assert sr.residual(S, [2.0, 0.0, 4.0], [1.0, 0.0, 2.0], rows=np.array([1, 1, 0], bool)) == 0.0
     assert sr.residual(np.zeros((1, 1)), [0.0], [0.0]) == 0.0
+
+
+def _banded_blocks(m, na, track, seed, integers=False):
+    """A random block-banded system as the getter returns one: every pair
+    j >= k with j - k < track once, in shuffled order; the strict upper triangle
+    of a diagonal block is junk that nobody may read.  integers: entries that
+    are multiples of 2^-10 below 16, the diagonal dominant."""
+    rng = np.random.default_rng(seed)
+    jk = np.array([(j, k) for j in range(m) for k in range(max(0, j - track + 1), j + 1)])
+    jk = jk[rng.permutation(len(jk))]
+    if integers:
+        blocks = rng.integers(-(1 << 13), 1 << 13, (len(jk), na, na)) / 1024.0
+    else:
+        blocks = rng.standard_normal((len(jk), na, na))
+        blocks *= 10.0 ** rng.integers(-3, 4, (len(jk), 1, 1))
+    for b in np.flatnonzero(jk[:, 0] == jk[:, 1]):
+        blocks[b] += np.triu(np.full((na, na), 1e300), 1)
+        if integers:
+            blocks[b][np.diag_indices(na)] = float(1 << 12) + rng.integers(0, 64, na)
+    return jk, blocks
+
+
+def _dense_lower(m, na, jk, blocks):
+    """The dense S of tests/test_gpu_stage_ref.py::test_solve_stage."""
+    S = np.zeros((na * m, na * m))
+    for (j, k), B in zip(jk, blocks):
+        S[na * j:na * j + na, na * k:na * k + na] = np.tril(B) if j == k else B
+    return S
+
+
+@pytest.mark.parametrize("m,na,track", [(23, 6, 9), (17, 9, 6), (11, 12, 5), (5, 7, 1)])
+def test_residual_blocks_is_the_dense_residual(m, na, track):
+    """residual_blocks against residual on the dense S test_solve_stage
+    builds, with a row mask, an unobserved camera (zero rows and columns, zero
+    e_ and da: 0 / 0 counts as satisfied).  Not to the
+    last bit: a row's terms are added block by block and not column by column,
+    so each sum carries its own rounding -- within residual_slack of each
+    other, which is below 1e-2 of ld * u here.  da is an fp64 solve of the
+    system, so eta is the small number it is in use."""
+    rng = np.random.default_rng(m)
+    jk, blocks = _banded_blocks(m, na, track, seed=na)
+    ld = na * m
+    e = rng.standard_normal(ld)
+    dead = m // 2
+    blocks[(jk[:, 0] == dead) | (jk[:, 1] == dead)] = 0.0
+    e[na * dead:na * dead + na] = 0.0
+    Sfull = sr.symmetrise(_dense_lower(m, na, jk, blocks))
+    live = np.repeat(np.arange(m) != dead, na)
+    x = np.zeros(ld)
+    x[live] = np.linalg.solve(Sfull[np.ix_(live, live)], e[live])
+    da = np.asfortranarray(x.reshape(na, m, order="F"))
+    rows = rng.random(ld) < 0.8
+    rows[na * dead:na * dead + na] = True
+    S = _dense_lower(m, na, jk, blocks)
+    terms = na * (2 * track - 1)
+    for mask in (None, rows, np.zeros(ld, bool)):
+        want, got = sr.residual(S, e, da, mask), sr.residual_blocks(m, na, jk, blocks, e, da, mask)
+        slack = sr.residual_slack(terms, want)
+        print(f"m {m} na {na} track {track}: dense {want:.17g} blocks {got:.17g} "
+              f"slack {slack:.3g} = {slack / (ld * sr.U53):.3g} ld u")
+        assert np.isfinite(want) and abs(got - want) <= slack
+        assert want < 1e-6 and slack <= 1e-2 * ld * sr.U53
+    assert sr.residual_blocks(m, na, jk, blocks, e, da, np.zeros(ld, bool)) == 0.0
+    # a right-hand side on a row with nothing in it is a whole miss, in both
+    e[na * dead] = 1.0
+    assert sr.residual(S, e, da) == 1.0 == sr.residual_blocks(m, na, jk, blocks, e, da)
+    # the small cases of test_residual_rows_and_exact_zeros
+    one = np.array([[0, 0], [1, 1], [2, 2]]), np.array([2.0, 0.0, 4.0]).reshape(3, 1, 1)
+    assert sr.residual_blocks(3, 1, *one, [2.0, 0.0, 4.0], [1.0, 0.0, 1.0]) == 0.0
+    assert sr.residual_blocks(3, 1, *one, [2.0, 0.0, 4.0], [1.0, 0.0, 2.0]) > 0.1
+    assert sr.residual_blocks(3, 1, *one, [2.0, 0.0, 4.0], [1.0, 0.0, 2.0],
+                              rows=np.array([1, 1, 0], bool)) == 0.0
+
+
+@pytest.mark.parametrize("m,na,track", [(23, 6, 9), (11, 12, 5)])
+def test_residual_blocks_notices_one_entry(m, na, track):
+    """An exact solution: S in multiples of 2^-10 below 2^13, x integers below
+    2^10, so e_ = S x is exact in fp64 (every product and partial sum fits 53
+    bits) and both residuals are exactly zero.  One entry of x off by a relative
+    1e-12 lifts row r to |S_rr x_r| 1e-12 / (|S||x| + |e_|)_r on the dominant
+    diagonal: 4096 <= |S_rr| < 4160, the row's other entries (at most 131, each
+    at most 8) sum to 1048 at the most and 512 <= |x| < 1024, so the quotient is
+    at least 4096 * 512 / (2 * 5208 * 1024) = 0.19 -- eta >= 1.9e-13 against
+    ld * u = 1.5e-14."""
+    rng = np.random.default_rng(7)
+    jk, blocks = _banded_blocks(m, na, track, seed=1, integers=True)
+    ld = na * m
+    S = _dense_lower(m, na, jk, blocks)
+    x = rng.integers(512, 1024, ld).astype(np.float64) * rng.choice([-1.0, 1.0], ld)
+    e = sr.symmetrise(S) @ x
+    assert np.array_equal(e.astype(sr.LD), sr.symmetrise(S).astype(sr.LD) @ x.astype(sr.LD))
+    da = np.asfortranarray(x.reshape(na, m, order="F"))
+    assert sr.residual_blocks(m, na, jk, blocks, e, da) == 0.0 == sr.residual(S, e, da)
+    bar = ld * sr.U53
+    for r in (0, ld // 2 + 1, ld - 1):
+        bad = x.copy()
+        bad[r] *= 1 + 1e-12
+        bad = bad.reshape(na, m, order="F")
+        eta = sr.residual_blocks(m, na, jk, blocks, e, bad)
+        print(f"m {m} na {na}: row {r} off by 1e-12: eta / (ld u) {eta / bar:.3g}")
+        assert eta > bar and eta >= 1.9e-13
+        assert abs(eta - sr.residual(S, e, bad)) <= sr.residual_slack(na * (2 * track - 1), eta)
+        # ... and a mask that leaves out every row the entry couples to does not see it
+        j = r // na
+        far = np.repeat(np.abs(np.arange(m) - j) >= track, na)
+        assert sr.residual_blocks(m, na, jk, blocks, e, bad, far) == 0.0
 
 
 # ---------------------------------------------------------------------------

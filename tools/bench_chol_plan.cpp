@@ -2,16 +2,18 @@
 // csrc/ba_chol_plan.cpp chol_plan_build / chol_nd_step on the co-visible block
 // set of a problem read from a file.  The block set is built as a context
 // builds it (csrc/ba_plan.cpp: observation sort, track-kind point order,
-// plan_host), then planned for num_a 6, 7, 10, 12 and the solver modes 0 (auto)
-// .. 4 on devices of the given compute-unit counts.  One "chol" line each with
+// plan_host), then planned for num_a 6, 7, 10, 12 (or --na's) and the solver modes
+// 0 (auto) .. 4 on devices of the given compute-unit counts.  One "chol" line each with
 // the plan's scalars and three FNV-1a values: "solveplan" (every plan vector
 // and scalar), "launchplan" (the stored cr32_fplan and chol_nd_step of every
 // step, runner off) and "launchrun" (the same with the runner on).
 // tests/test_solve_plan.py pins them, tests/test_plan_sanitize.py runs this
 // program under the sanitizers.
 //
-// usage: bench_chol_plan [--ncu NCU[,NCU...]] [--dump DIR] [--nd-verbose] problem.bin ...
+// usage: bench_chol_plan [--ncu NCU[,NCU...]] [--na NA[,NA...]] [--dump DIR] [--nd-verbose]
+//                        problem.bin ...
 //   --ncu         default 256 (the MI355X)
+//   --na          the camera sizes to plan, 1 .. 32 each; default 6,7,10,12
 //   --dump DIR    each plan's vectors as int32 files
 //   --nd-verbose  the nested dissection's decision (VLGBA_ND=v) on stderr
 // Build (tools/bench_plan.sh), with any C++17 compiler:
@@ -124,7 +126,7 @@ int dump_plan(const chol_plan &P, const std::vector<int> &jk, const std::string 
     return std::fclose(f);
 }
 struct chol_opts {
-    std::vector<int> ncu;
+    std::vector<int> ncu, na;
     std::string dump;
     bool nd_verbose = false;
 };
@@ -134,7 +136,7 @@ int chol_plans(const char *file, int m, const std::vector<int> &jk, const chol_o
     stem = stem.substr(stem.find_last_of('/') + 1);
     stem = stem.substr(0, stem.find_last_of('.'));
     for (int ncu : o.ncu)
-        for (int na : {6, 7, 10, 12})
+        for (int na : o.na)
             for (int mode = 0; mode <= 4; mode++) {
                 chol_plan_in in{};
                 in.m = m;
@@ -220,6 +222,9 @@ int main(int argc, char **argv)
         if (!std::strcmp(argv[q], "--ncu") && q + 1 < argc) {
             for (const char *s = argv[++q]; *s; s += std::strcspn(s, ","), s += *s == ',')
                 chol.ncu.push_back(std::max(1, std::atoi(s)));
+        } else if (!std::strcmp(argv[q], "--na") && q + 1 < argc) {
+            for (const char *s = argv[++q]; *s; s += std::strcspn(s, ","), s += *s == ',')
+                chol.na.push_back(std::min(32, std::max(1, std::atoi(s))));
         } else if (!std::strcmp(argv[q], "--dump") && q + 1 < argc) {
             chol.dump = argv[++q];
         } else if (!std::strcmp(argv[q], "--nd-verbose")) {
@@ -229,9 +234,10 @@ int main(int argc, char **argv)
         }
     }
     if (chol.ncu.empty()) chol.ncu.push_back(256);
+    if (chol.na.empty()) chol.na = {6, 7, 10, 12};
     if (files.empty()) {
-        std::fprintf(stderr, "usage: bench_chol_plan [--ncu NCU[,NCU...]] [--dump DIR] "
-                             "[--nd-verbose] problem.bin ...\n");
+        std::fprintf(stderr, "usage: bench_chol_plan [--ncu NCU[,NCU...]] [--na NA[,NA...]] "
+                             "[--dump DIR] [--nd-verbose] problem.bin ...\n");
         return 2;
     }
     for (const char *file : files) {
