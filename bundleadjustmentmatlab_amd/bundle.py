@@ -756,6 +756,36 @@ def _block_mode(radial, jacobian, loss, loss_scale, return_residuals):
     return ex, JACOBIANS[jacobian], LOSSES[loss], float(loss_scale)
 
 
+def _block_solve(name, head, head_ex, mode, x, count, N, residuals, return_stats, device,
+                 max_iter, max_iter2, lambda0, stop_rel):
+    """The call both batched one-block functions make: ``name`` (head..., opt, x,
+    error_, ..., stats), or with mode = (True, jacobian, loss, scale) ``name``_ex
+    (head_ex..., opt, jacobian, loss, scale, x, error_, ..., res, w, stats), on
+    ``count`` problems with N observations in all; x (the parameters) is
+    updated in place.  residuals: None, or what turns res (N x 2) and w (N) into
+    the returned residuals.  Returns the outputs after the parameters:
+    (errs[, stats][, residuals])."""
+    ex, jac, lk, ls = mode
+    cap = (max_iter if max_iter > 0 else 20) + 1
+    err = np.zeros((count, cap))
+    nerr = np.zeros(count, dtype=np.int32)
+    opt = VlgbaOptions()
+    opt.max_iter, opt.max_iter2, opt.lambda0 = int(max_iter), int(max_iter2), float(lambda0)
+    opt.device, opt.stop_rel = int(device), float(stop_rel)
+    st = VlgbaStats()
+    tail = (_dp(x), _dp(err), cap, nerr.ctypes.data_as(c_ip))
+    if not ex:
+        check(getattr(lib(), name)(*head, ctypes.byref(opt), *tail, ctypes.byref(st)), name)
+    else:
+        res, wts = np.zeros((N, 2)), np.zeros(N)
+        check(getattr(lib(), name + "_ex")(*head_ex, ctypes.byref(opt), jac, lk, ls, *tail,
+                                           _dp(res) if residuals else None,
+                                           _dp(wts) if residuals else None, ctypes.byref(st)),
+              name + "_ex")
+    out = ([err[q, : nerr[q]].copy() for q in range(count)],) + ((st,) if return_stats else ())
+    return out + (residuals(res, wts),) if residuals else out
+
+
 def bundle_euclid_resect(K, Te, w, Xs, xs, *varargin, device=0, max_iter=0, max_iter2=0,
                          lambda0=0.0, stop_rel=0.0, return_stats=False, radial=None,
                          jacobian=None, loss="none", loss_scale=0.0, return_residuals=False):
@@ -784,7 +814,7 @@ def bundle_euclid_resect(K, Te, w, Xs, xs, *varargin, device=0, max_iter=0, max_
     order: K_, Te_, w_, errs[, stats][, residuals][, kd_]."""
     K, Te, w = _F(K), _F(Te), _F(w)
     c = w.shape[1]
-    ex, jac, lk, ls = _block_mode(radial, jacobian, loss, loss_scale, return_residuals)
+    mode = _block_mode(radial, jacobian, loss, loss_scale, return_residuals)
     o = parse_options(c, 0, varargin)
     nvk = o["num_variableK"] if radial is None else RADIAL_NVK
     na = 6 + nvk
@@ -797,33 +827,19 @@ def bundle_euclid_resect(K, Te, w, Xs, xs, *varargin, device=0, max_iter=0, max_
                                              if c else np.zeros((0, 3))))
     xo = np.ascontiguousarray(np.concatenate([np.asarray(x, dtype=np.float64)[:2].T for x in xs]
                                              if c else np.zeros((0, 2))))
-    cap = (max_iter if max_iter > 0 else 20) + 1
-    err = np.zeros((c, cap))
-    nerr = np.zeros(c, dtype=np.int32)
+    Kc = np.ascontiguousarray(K.reshape(-1, order="F"))
     pr = VlgbaResectProblem(c, na, ptr.ctypes.data_as(ctypes.POINTER(ctypes.c_longlong)),
-                            _dp(Xo), _dp(xo), _dp(np.ascontiguousarray(K.reshape(-1, order="F"))))
-    opt = VlgbaOptions()
-    opt.max_iter, opt.max_iter2, opt.lambda0 = int(max_iter), int(max_iter2), float(lambda0)
-    opt.device, opt.stop_rel = int(device), float(stop_rel)
-    st = VlgbaStats()
-    if not ex:
-        check(lib().vlgba_resect(ctypes.byref(pr), ctypes.byref(opt), _dp(a), _dp(err), cap,
-                                 nerr.ctypes.data_as(c_ip), ctypes.byref(st)), "vlgba_resect")
-    else:
-        res = np.zeros((int(ptr[-1]), 2))
-        wts = np.zeros(int(ptr[-1]))
-        check(lib().vlgba_resect_ex(ctypes.byref(pr), ctypes.byref(opt), jac, lk, ls, _dp(a),
-                                    _dp(err), cap, nerr.ctypes.data_as(c_ip),
-                                    _dp(res) if return_residuals else None,
-                                    _dp(wts) if return_residuals else None, ctypes.byref(st)),
-              "vlgba_resect_ex")
+                            _dp(Xo), _dp(xo), _dp(Kc))
+
+    def per_camera(res, wts):
+        return [(res[ptr[q]:ptr[q + 1]].T.copy(), wts[ptr[q]:ptr[q + 1]].copy())
+                for q in range(c)]
+    out = _block_solve("vlgba_resect", (ctypes.byref(pr),), (ctypes.byref(pr),), mode, a, c,
+                       int(ptr[-1]), per_camera if return_residuals else None, return_stats,
+                       device, max_iter, max_iter2, lambda0, stop_rel)
     a = a.reshape(na, c, order="F")
     K_, Te_, w_, _ = unpack(K, a, np.zeros((3, 0)), np.zeros((1, 0)), nvk)
-    errs = [err[q, : nerr[q]].copy() for q in range(c)]
-    out = (K_, Te_, w_, errs) + ((st,) if return_stats else ())
-    if return_residuals:
-        out += ([(res[ptr[q]:ptr[q + 1]].T.copy(), wts[ptr[q]:ptr[q + 1]].copy())
-                 for q in range(c)],)
+    out = (K_, Te_, w_) + out
     if radial is not None:
         out += (a[7:9].copy(order="F"),)
     return out
@@ -902,38 +918,20 @@ def bundle_euclid_intersect(K, Te, w, X, obs_ptr, obs_cam, obs_x, device=0, max_
     as triangulate_points, ``jacobian``, ``loss`` / ``loss_scale`` and
     ``return_residuals`` as bundle_euclid_resect; the residuals are one pair
     (e (N x 2), w (N)) in the order of obs_x, appended last."""
-    ex, jac, lk, ls = _block_mode(radial, jacobian, loss, loss_scale, return_residuals)
+    mode = _block_mode(radial, jacobian, loss, loss_scale, return_residuals)
     keep, args = _tracks(K, Te, w, obs_ptr, obs_cam, obs_x)
     n = args[4]
     X = np.asarray(X, dtype=np.float64)
     assert X.shape[0] in (3, 4) and X.shape[1] == n
     b = np.ascontiguousarray(X[:3].T).reshape(-1)      # 3 x n column major
-    cap = (max_iter if max_iter > 0 else 20) + 1
-    err = np.zeros((n, cap))
-    nerr = np.zeros(n, dtype=np.int32)
-    opt = VlgbaOptions()
-    opt.max_iter, opt.max_iter2, opt.lambda0 = int(max_iter), int(max_iter2), float(lambda0)
-    opt.device, opt.stop_rel = int(device), float(stop_rel)
-    st = VlgbaStats()
-    if not ex:
-        check(lib().vlgba_intersect(*args, ctypes.byref(opt), _dp(b), _dp(err), cap,
-                                    nerr.ctypes.data_as(c_ip), ctypes.byref(st)),
-              "vlgba_intersect")
-    else:
-        N = len(keep[4])
-        res, wts = np.zeros((N, 2)), np.zeros(N)
-        kd = None if radial is None else _radial_kd(radial, args[0])
-        check(lib().vlgba_intersect_ex(*args[:4], None if kd is None else _dp(kd), *args[4:],
-                                       ctypes.byref(opt), jac, lk, ls, _dp(b), _dp(err), cap,
-                                       nerr.ctypes.data_as(c_ip),
-                                       _dp(res) if return_residuals else None,
-                                       _dp(wts) if return_residuals else None, ctypes.byref(st)),
-              "vlgba_intersect_ex")
+    kd = None if radial is None else _radial_kd(radial, args[0])
+    out = _block_solve("vlgba_intersect", args,
+                       args[:4] + (None if kd is None else _dp(kd),) + args[4:], mode, b, n,
+                       len(keep[4]), (lambda res, wts: (res, wts)) if return_residuals else None,
+                       return_stats, device, max_iter, max_iter2, lambda0, stop_rel)
     X_ = np.array(X, order="F")
     X_[:3] = b.reshape(n, 3).T
-    errs = [err[q, : nerr[q]].copy() for q in range(n)]
-    out = (X_, errs) + ((st,) if return_stats else ())
-    return out + ((res, wts),) if return_residuals else out
+    return (X_,) + out
 
 
 # ---------------------------------------------------------------------------

@@ -1,40 +1,33 @@
-// ba_batch_lm.h -- host side of the batched one-block LM entries
-// (vlgba_resect in ba_resect.hip: one camera, structure fixed; vlgba_intersect
-// in ba_triang.hip: one point, motion fixed): the LM control of
-// bundle_euclid.m:120-123, 205-241 applied per problem, each with its own
-// lambda, and the per-device pool of a stream and a pinned staging block.
+// ba_batch_lm.h -- the batched one-block LM, host only: the LM control of
+// bundle_euclid.m:120-123, 205-241 applied per problem, each with its own lambda
+// (batch_lm), and the loop that drives a backend with it (batch_lm_run).  No
+// HIP here: vlgba_resect[_ex] (ba_resect.hip: one camera, structure fixed) and
+// vlgba_intersect[_ex] (ba_triang.hip: one point, motion fixed) run it on the
+// device backend of ba_batch_dev.h, tests/native/block_host.cpp on a CPU one.
 //
-// Protocol of a pass.  stage() decides which problems go on (:120-123) and
-// writes lambda and the flags word of every problem (as doubles, one copy a
-// pass) into the pinned block; the pass kernel reads them with device-scope
-// vector loads and writes four doubles per problem: old SSE, new SSE,
-// dp'(lambda dp + g), pinv flag.  apply() reads those and applies :218-241.
-// Under a loss (vlgba_resect_ex, vlgba_intersect_ex) the pass reports the robust
-// cost and gradient in the same places; nothing here changes.
+// Protocol of a pass, the contract between the driver and a backend.  The driver
+// owns a staging block of 6 np doubles, lam [np] | flags [np] | out [4 np]
+// (flags == lam + np: a backend may move both in one copy).  stage() decides
+// which problems go on (:120-123) and writes lambda and the flags word of every
+// problem, as doubles; backend.pass(lam, flags, out) runs every problem whose
+// flags has bit 1 and writes four doubles for it -- old cost, new cost,
+// dp'(lambda dp + g), 1.0 if the step came from the pinv fallback else 0.0 --
+// leaving the four of a finished problem alone; apply() applies :218-241.  The
+// backend keeps two parameter sets per problem, x (the linearisation point) and
+// x_new (the last step's), and takes x_new as x first when told that the
+// previous pass was accepted; after the last pass backend.fetch hands back both
+// and the driver picks.  Under a loss the pass reports the robust cost and
+// gradient in the same places; nothing here changes.
 //   flags: 1 active | 2 linearise again (the parameters changed) | 4 the
 //          previous pass was accepted (take x_new as x first)
 #pragma once
 #include "../../include/vlgba.h"
-
-#include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <chrono>
 #include <cmath>
 #include <cstring>
 #include <vector>
-
-// Per-device pool of a stream and a pinned host block for the per-pass LM
-// scalars: creating a stream and pageable copies cost more than the
-// resection itself (the growing-BA replay calls it once per added camera).
-struct rs_pool {
-    int device;
-    hipStream_t s;
-    double *pin;     // pinned: lam [np] | flags [np] (as doubles) | out [4 np]
-    size_t cap;      // doubles
-};
-int rs_acquire(int device, size_t need, rs_pool &r);   // ba_resect.hip
-void rs_release(const rs_pool &r);
 
 // the mode arguments of the _ex entries: the kinds of vlgba_set_jacobian and
 // vlgba_set_loss and the latter's scale rule; the radial model is analytic only
@@ -55,7 +48,7 @@ struct batch_lm {
     std::vector<double> lam, nu;
     std::vector<int> fl, iter, iter2, passes, acc, active, accepted_prev, relin;
     std::vector<std::vector<double>> err;
-    int total_passes = 0, total_acc = 0;
+    int total_passes = 0, total_acc = 0, total_pinv = 0;
 
     // opt: max_iter, max_iter2, lambda0, stop_rel (0 -> the reference's)
     batch_lm(size_t np_, const vlgba_options *opt)
@@ -106,6 +99,7 @@ struct batch_lm {
             const double rho = (old - nw) / dpg;
             passes[q]++;
             total_passes++;
+            total_pinv += out[4 * q + 3] != 0.0;   // the step came from the pinv fallback
             if ((old - nw) > 0) {   // bundle_euclid.m:218-232
                 const double olde = old / num_vis, newe = nw / num_vis;
                 if ((int)err[q].size() < iter[q]) err[q].push_back(olde);
@@ -145,8 +139,44 @@ struct batch_lm {
         stats->accepted = total_acc;
         stats->num_error = 0;
         stats->lambda = np ? lam[0] : 0.0;
-        stats->pinv_passes = stats->spin_retries = stats->nd_retries = 0;
+        stats->pinv_passes = total_pinv;
+        stats->spin_retries = stats->nd_retries = 0;
         stats->seconds =
             std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     }
 };
+
+// what runs the passes of np problems with nx parameters each (protocol above);
+// both return 0 or an error code, which ends the solve
+struct batch_backend {
+    virtual ~batch_backend() = default;
+    virtual int pass(const double *lam, const double *flags, double *out) = 0;
+    virtual int fetch(double *x, double *x_new) = 0;   // nx * np doubles each
+};
+
+// The LM of every problem of lm on be: x (nx * np) receives the parameters of
+// the last accepted step, error_out / num_error as write_errors, stats as
+// fill_stats (pinv_passes: the passes whose fourth scalar was set; apply() counts
+// them while it has the pass's scalars in hand -- a loop of its own here put
+// vlgba_intersect on 20 000 points 3 % above its time, profiles/block_host/).
+// stage: 6 np doubles.
+inline int batch_lm_run(batch_lm &lm, batch_backend &be, double *stage, int nx,
+                        const long long *obs_ptr, double *x, double *error_out, int error_cap,
+                        int *num_error, vlgba_stats *stats,
+                        std::chrono::steady_clock::time_point t0)
+{
+    const size_t np = lm.np;
+    double *lam = stage, *flags = stage + np, *out = stage + 2 * np;
+    int rc = 0;
+    while (!rc && lm.stage(lam, flags))
+        if (!(rc = be.pass(lam, flags, out))) lm.apply(out, obs_ptr);
+    std::vector<double> xn((size_t)nx * np);
+    if (!rc && !(rc = be.fetch(x, xn.data()))) {
+        for (size_t q = 0; q < np; q++)   // the last accepted step's parameters
+            if (lm.accepted_prev[q])
+                std::memcpy(x + (size_t)nx * q, xn.data() + (size_t)nx * q, sizeof(double) * nx);
+        lm.write_errors(error_out, error_cap, num_error);
+    }
+    lm.fill_stats(stats, t0);
+    return rc;
+}

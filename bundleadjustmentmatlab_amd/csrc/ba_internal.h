@@ -296,6 +296,56 @@ void *ba_dmalloc(size_t bytes);   // per-device caching allocator (ba_solver.cpp
 // per (kernel, device), thread-safe; ba_solver.cpp)
 int ba_ensure_dyn_lds(const void *fn, size_t bytes);
 void ba_dfree(void *p);
+// Typed device memory on that allocator and the asynchronous copies on a
+// stream: 0 or -(int)hipError, as VLGBA_CHECK.  A count of 0 allocates one
+// element and copies nothing.
+template <typename T>
+inline int dalloc(T **p, size_t count)
+{
+    *p = (T *)ba_dmalloc(sizeof(T) * (count ? count : 1));
+    return *p ? 0 : -(int)hipErrorOutOfMemory;
+}
+template <typename T>
+inline int upload(T *dst, const T *src, size_t count, hipStream_t s)
+{
+    if (count == 0) return 0;
+    return -(int)hipMemcpyAsync(dst, src, sizeof(T) * count, hipMemcpyHostToDevice, s);
+}
+template <typename T>
+inline int download(T *dst, const T *src, size_t count, hipStream_t s)
+{
+    if (count == 0) return 0;
+    return -(int)hipMemcpyAsync(dst, src, sizeof(T) * count, hipMemcpyDeviceToHost, s);
+}
+// move-only owner of one such block (freed with it; alloc() again replaces it).
+// Work queued on a stream must have drained before the owner goes.
+template <typename T>
+class ba_dbuf {
+    T *p_ = nullptr;
+
+public:
+    ba_dbuf() = default;
+    ba_dbuf(ba_dbuf &&o) noexcept : p_(o.p_) { o.p_ = nullptr; }
+    ba_dbuf &operator=(ba_dbuf &&o) noexcept
+    {
+        if (this != &o) {
+            ba_dfree(p_);
+            p_ = o.p_;
+            o.p_ = nullptr;
+        }
+        return *this;
+    }
+    ba_dbuf(const ba_dbuf &) = delete;
+    ba_dbuf &operator=(const ba_dbuf &) = delete;
+    ~ba_dbuf() { ba_dfree(p_); }
+    int alloc(size_t count)
+    {
+        ba_dfree(p_);
+        return dalloc(&p_, count);
+    }
+    T *get() const { return p_; }
+    operator T *() const { return p_; }
+};
 // after a re-solve: did one of the runner's own hand-offs time out?  Then the
 // runner is off for this context (1); 0: no; < 0: error (ba_chol.hip)
 int ba_env_runner_timed_out(ba_dev *d);

@@ -15,29 +15,31 @@
 // dp'(lambda dp + g) with the point entries exact zeros.  Every sum here runs
 // sequentially in the reference's order (observations ascending) and the 6 x 6
 // (num_a x num_a) solve is the parity-mode sequential Cholesky (pinv by cyclic
-// Jacobi on a non-positive pivot), so each problem's trajectory equals the
-// oracle's bundle_euclid restatement with m = 1 (vinv formula, solve / sums
+// Jacobi on a non-positive pivot: ba_small_solve.h, host and device; such a
+// pass counts in vlgba_stats.pinv_passes), so each problem's trajectory equals
+// the oracle's bundle_euclid restatement with m = 1 (vinv formula, solve / sums
 // sequential) bit for bit.
 //
 // One workgroup per camera and LM pass: observations in tiles of 256 (one lane
 // each: projection + num_a forward-difference columns into LDS), then
 // NA*NA + NA + 1 accumulator lanes walk the tile in order.  The LM control
 // (bundle_euclid.m:205-241, glibc pow for the lambda rule) stays on the host,
-// per problem, exactly as vlgba_run applies it (ba_batch_lm.h, shared with the
-// per-point dual vlgba_intersect of ba_triang.hip).
+// per problem, exactly as vlgba_run applies it: the driver of ba_batch_lm.h on
+// the device backend of ba_batch_dev.h, both shared with the per-point dual
+// vlgba_intersect of ba_triang.hip.  resect_run checks the arguments, uploads
+// the problem and hands over a launch and a residual lambda.
 //
 // vlgba_resect_ex (include/vlgba.h) runs the same pass with the fused path's
 // analytic Jacobians, radial-distortion camera (num_a = 9) and robust losses:
 // further instantiations of k_resect_pass (below), the same host control.
 #include "ba_camera.h"
-#include "ba_batch_lm.h"
+#include "ba_batch_dev.h"
+#include "ba_small_solve.h"
 #include "../../include/vlgba.h"
 
 #include <chrono>
-#include <cmath>
 #include <cstring>
-#include <mutex>
-#include <vector>
+#include <type_traits>
 
 #define RS_TILE 256
 
@@ -70,6 +72,21 @@ __device__ __forceinline__ void resect_project_new(const double *k4, const doubl
         vlg_calib(Kc, k4, an, NA - 6);
         vlg_project(Kc, rotn, an + 3, b, xh);
     }
+}
+
+// Under a loss: the two terms t[0], t[1] the cost lane adds for the residual
+// (e0, e1), so that its serial loop stays free of branches -- a plain term's
+// e0 e0 and e1 e1, as the plain pass adds them, else rho and an exact + 0.
+// Returns sqrt(w).
+__device__ __forceinline__ double resect_cost_terms(ba_loss ls, double e0, double e1, double *t)
+{
+    const double s = e0 * e0 + e1 * e1;
+    double rho, sw;
+    vlg_loss(ls.kind, ls.c, s, &rho, &sw);
+    const bool plain = vlg_loss_plain(ls.kind, ls.c, s);
+    t[0] = plain ? e0 * e0 : rho;
+    t[1] = plain ? e1 * e1 : 0.0;
+    return sw;
 }
 
 template <int NA, bool JAC, bool LOSS>
@@ -140,18 +157,10 @@ __global__ __launch_bounds__(256) void k_resect_pass(
                 row[2 * NA] = xo[2 * o] - xh[0];          // e = X - X_hat (:222-223)
                 row[2 * NA + 1] = xo[2 * o + 1] - xh[1];
                 if constexpr (LOSS) {
-                    const double e0 = row[2 * NA], e1 = row[2 * NA + 1];
-                    const double s = e0 * e0 + e1 * e1;
-                    double rho, sw;
-                    vlg_loss(ls.kind, ls.c, s, &rho, &sw);
+                    const double sw = resect_cost_terms(ls, row[2 * NA], row[2 * NA + 1],
+                                                        row + 2 * NA + 2);
 #pragma unroll 1
                     for (int k = 0; k < 2 * NA + 2; k++) row[k] *= sw;
-                    // the two terms the cost lane adds, so that its serial loop
-                    // stays free of branches: a plain term's e0 e0 and e1 e1, as
-                    // the plain pass adds them, else rho and an exact + 0
-                    const bool plain = vlg_loss_plain(ls.kind, ls.c, s);
-                    row[2 * NA + 2] = plain ? e0 * e0 : rho;
-                    row[2 * NA + 3] = plain ? e1 * e1 : 0.0;
                 }
             }
             __syncthreads();
@@ -182,109 +191,8 @@ __global__ __launch_bounds__(256) void k_resect_pass(
     if (tid < NUE) st[tid] = stg[tid];
     __syncthreads();
     const double lambda = __hip_atomic_load(lam_p + pb, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (tid == 0) {
-        // S = U* (damped diagonal), e_ = eA - 0: fix_structure zeroes V, W, eB,
-        // so V*^-1 = pinv(0) = 0 and Y = 0 (bundle_euclid.m:140-193)
-        for (int c = 0; c < NA; c++)
-            for (int r = 0; r < NA; r++) {
-                const double u = st[r + NA * c];
-                S[r + NA * c] = (r == c) ? (1 + lambda) * u : u;
-            }
-        for (int r = 0; r < NA; r++) rhs[r] = st[NA * NA + r];
-        // pinv rule for exactly-zero rows (App. A Q2 / Q8), then the sequential
-        // Cholesky of the lower triangle (the parity-mode solve's loops)
-        for (int j = 0; j < NA; j++)
-            if (S[j + NA * j] == 0.0) {
-                S[j + NA * j] = 1.0;
-                rhs[j] = 0.0;
-            }
-        double L[NA * NA];
-        for (int q = 0; q < NA * NA; q++) L[q] = S[q];
-        bool ok = true;
-        for (int j = 0; j < NA && ok; j++) {
-            double s = L[j + NA * j];
-            for (int k = 0; k < j; k++) s = s - L[j + NA * k] * L[j + NA * k];
-            if (!(s > 0.0)) {
-                ok = false;
-                break;
-            }
-            const double p = sqrt(s);
-            L[j + NA * j] = p;
-            for (int i = j + 1; i < NA; i++) {
-                double t = L[i + NA * j];
-                for (int k = 0; k < j; k++) t = t - L[i + NA * k] * L[j + NA * k];
-                L[i + NA * j] = t / p;
-            }
-        }
-        if (ok) {
-            double x[NA];
-            for (int i = 0; i < NA; i++) {
-                double t = rhs[i];
-                for (int k = 0; k < i; k++) t = t - L[i + NA * k] * x[k];
-                x[i] = t / L[i + NA * i];
-            }
-            for (int i = NA - 1; i >= 0; i--) {
-                double t = x[i];
-                for (int k = i + 1; k < NA; k++) t = t - L[k + NA * i] * x[k];
-                x[i] = t / L[i + NA * i];
-            }
-            for (int i = 0; i < NA; i++) da[i] = x[i];
-        } else {
-            // da = pinv(S) e_ (bundle_euclid.m:193): cyclic Jacobi on the
-            // symmetrised S, MATLAB's tolerance NA * eps(max |eigenvalue|)
-            double A[NA][NA], Q[NA][NA];
-            for (int p = 0; p < NA; p++)
-                for (int q = 0; q < NA; q++) {
-                    const double sp = p >= q ? S[p + NA * q] : S[q + NA * p];
-                    A[p][q] = sp;
-                    Q[p][q] = p == q ? 1.0 : 0.0;
-                }
-            for (int sweep = 0; sweep < 64; sweep++) {
-                double off = 0.0;
-                for (int p = 0; p < NA; p++)
-                    for (int q = p + 1; q < NA; q++) off += A[p][q] * A[p][q];
-                if (off == 0.0) break;
-                for (int p = 0; p < NA - 1; p++)
-                    for (int q = p + 1; q < NA; q++) {
-                        if (A[p][q] == 0.0) continue;
-                        const double th = (A[q][q] - A[p][p]) / (2.0 * A[p][q]);
-                        const double t = (th >= 0.0 ? 1.0 : -1.0) /
-                                         (fabs(th) + sqrt(th * th + 1.0));
-                        const double c = 1.0 / sqrt(t * t + 1.0), sn = t * c;
-                        for (int k = 0; k < NA; k++) {
-                            const double u = A[k][p], v = A[k][q];
-                            A[k][p] = c * u - sn * v;
-                            A[k][q] = sn * u + c * v;
-                        }
-                        for (int k = 0; k < NA; k++) {
-                            const double u = A[p][k], v = A[q][k];
-                            A[p][k] = c * u - sn * v;
-                            A[q][k] = sn * u + c * v;
-                        }
-                        for (int k = 0; k < NA; k++) {
-                            const double u = Q[k][p], v = Q[k][q];
-                            Q[k][p] = c * u - sn * v;
-                            Q[k][q] = sn * u + c * v;
-                        }
-                    }
-            }
-            double emax = 0.0;
-            for (int k = 0; k < NA; k++) emax = fmax(emax, fabs(A[k][k]));
-            int e;
-            (void)frexp(emax, &e);
-            const double tol = emax > 0.0 ? NA * ldexp(1.0, e - 53) : 0.0;
-            double x[NA] = {};
-            for (int k = 0; k < NA; k++) {
-                if (!(fabs(A[k][k]) > tol)) continue;
-                double w = 0.0;
-                for (int i = 0; i < NA; i++) w += Q[i][k] * rhs[i];
-                w /= A[k][k];
-                for (int i = 0; i < NA; i++) x[i] += Q[i][k] * w;
-            }
-            for (int i = 0; i < NA; i++) da[i] = x[i];
-            fail = 1;
-        }
-    }
+    // S = U* (damped diagonal), e_ = eA, da = pinv(S) e_: ba_small_solve.h
+    if (tid == 0 && small_solve_damped<NA>(st, lambda, S, rhs, da)) fail = 1;
     __syncthreads();
     if (tid < NA) {   // a_new = a + da (mex_bundle_3_db_new.c:137-140)
         an[tid] = av[tid] + da[tid];
@@ -306,13 +214,8 @@ __global__ __launch_bounds__(256) void k_resect_pass(
             double xh[2];
             resect_project_new<NA>(k4, an, rotn, b, xh);
             const double e0 = xo[2 * o] - xh[0], e1 = xo[2 * o + 1] - xh[1];
-            if constexpr (LOSS) {   // the two terms of the cost, as above
-                const double s = e0 * e0 + e1 * e1;
-                double rho, sw;
-                vlg_loss(ls.kind, ls.c, s, &rho, &sw);
-                const bool plain = vlg_loss_plain(ls.kind, ls.c, s);
-                At[tid][0] = plain ? e0 * e0 : rho;
-                At[tid][1] = plain ? e1 * e1 : 0.0;
+            if constexpr (LOSS) {
+                (void)resect_cost_terms(ls, e0, e1, At[tid]);
             } else {
                 At[tid][0] = e0;
                 At[tid][1] = e1;
@@ -376,11 +279,17 @@ __global__ __launch_bounds__(256) void k_resect_residuals(
 }
 
 namespace {
-template <typename T>
-int dmalloc_n(T **p, size_t n)
+// f(std::integral_constant<int, NA>) at the runtime num_a, or VLGBA_E_ARG
+template <class F>
+int rs_dispatch_na(int na, F &&f)
 {
-    *p = (T *)ba_dmalloc(sizeof(T) * (n ? n : 1));
-    return *p ? 0 : -(int)hipErrorOutOfMemory;
+    switch (na) {
+    case 6: return f(std::integral_constant<int, 6>());
+    case 7: return f(std::integral_constant<int, 7>());
+    case 10: return f(std::integral_constant<int, 10>());
+    case BA_RAD_NA: return f(std::integral_constant<int, BA_RAD_NA>());
+    default: return VLGBA_E_ARG;
+    }
 }
 
 // the pass of one mode at the runtime num_a
@@ -394,30 +303,21 @@ struct rs_args {
     ba_loss ls;
 };
 
-template <int NA, bool JAC, bool LOSS>
-void rs_launch_one(const rs_args &g, hipStream_t s)
-{
-    k_resect_pass<NA, JAC, LOSS><<<g.np, 256, 0, s>>>(g.np, g.ptr, g.X, g.x, g.K, g.a, g.an, g.st,
-                                                      g.lam, g.fl, g.out, g.ls);
-}
-
 // 0, or VLGBA_E_ARG for a (num_a, mode) pair that has no kernel (the radial
 // model under forward differences): nothing is launched then
 template <bool JAC, bool LOSS>
 int rs_launch_na(int na, const rs_args &g, hipStream_t s)
 {
-    switch (na) {
-    case 6: rs_launch_one<6, JAC, LOSS>(g, s); return 0;
-    case 7: rs_launch_one<7, JAC, LOSS>(g, s); return 0;
-    case 10: rs_launch_one<10, JAC, LOSS>(g, s); return 0;
-    case BA_RAD_NA:
-        if constexpr (JAC) {
-            rs_launch_one<BA_RAD_NA, true, LOSS>(g, s);
+    return rs_dispatch_na(na, [&](auto c) {
+        constexpr int NA = decltype(c)::value;
+        if constexpr (JAC || NA != BA_RAD_NA) {
+            k_resect_pass<NA, JAC, LOSS><<<g.np, 256, 0, s>>>(
+                g.np, g.ptr, g.X, g.x, g.K, g.a, g.an, g.st, g.lam, g.fl, g.out, g.ls);
             return 0;
+        } else {
+            return (int)VLGBA_E_ARG;
         }
-        return VLGBA_E_ARG;
-    default: return VLGBA_E_ARG;
-    }
+    });
 }
 
 int rs_launch(int na, bool jac, const rs_args &g, hipStream_t s)
@@ -426,46 +326,7 @@ int rs_launch(int na, bool jac, const rs_args &g, hipStream_t s)
                               : rs_launch_na<true, false>(na, g, s);
     return g.ls.kind ? rs_launch_na<false, true>(na, g, s) : rs_launch_na<false, false>(na, g, s);
 }
-std::mutex g_rs_pool_mu;
-std::vector<rs_pool> g_rs_pool;
-}   // namespace
 
-int rs_acquire(int device, size_t need, rs_pool &r)
-{
-    {
-        std::lock_guard<std::mutex> lk(g_rs_pool_mu);
-        for (size_t q = 0; q < g_rs_pool.size(); q++)
-            if (g_rs_pool[q].device == device) {
-                r = g_rs_pool[q];
-                g_rs_pool.erase(g_rs_pool.begin() + (long)q);
-                break;
-            }
-    }
-    if (!r.s) {
-        r.device = device;
-        if (hipStreamCreateWithFlags(&r.s, hipStreamNonBlocking) != hipSuccess) return -1;
-    }
-    if (r.cap < need) {
-        if (r.pin) (void)hipHostFree(r.pin);
-        r.pin = nullptr;
-        r.cap = 0;
-        const size_t cap = need > 4096 ? need : 4096;
-        if (hipHostMalloc((void **)&r.pin, sizeof(double) * cap, hipHostMallocDefault) !=
-            hipSuccess)
-            return -1;
-        r.cap = cap;
-    }
-    return 0;
-}
-
-void rs_release(const rs_pool &r)
-{
-    (void)hipStreamSynchronize(r.s);
-    std::lock_guard<std::mutex> lk(g_rs_pool_mu);
-    g_rs_pool.push_back(r);
-}
-
-namespace {
 // vlgba_resect (ex false: num_a 6 / 7 / 10, forward differences, no loss) and
 // vlgba_resect_ex
 int resect_run(const vlgba_resect_problem *pr, const vlgba_options *opt, bool ex, int jacobian,
@@ -490,117 +351,44 @@ int resect_run(const vlgba_resect_problem *pr, const vlgba_options *opt, bool ex
     if (!opt) opt = &dflt;
     VLGBA_CHECK(hipSetDevice(opt->device));
     const auto t0 = std::chrono::steady_clock::now();
-    rs_pool pool{opt->device, nullptr, nullptr, 0};
-    if (rs_acquire(opt->device, 6 * (size_t)np, pool)) {
-        if (pool.s) rs_release(pool);
-        return -1;
-    }
-    hipStream_t s = pool.s;
-    double *h_lam = pool.pin, *h_fl = pool.pin + np, *h_out = pool.pin + 2 * (size_t)np;
-    const int NUE = na * na + na + 1;
-    long long *d_ptr = nullptr;
-    double *d_X = nullptr, *d_x = nullptr, *d_K = nullptr, *d_a = nullptr, *d_an = nullptr;
-    double *d_st = nullptr, *d_lam = nullptr, *d_out = nullptr, *d_fl = nullptr, *d_res = nullptr;
-    int rc = 0;
+    // before the stream's guard: freed after it has drained (ba_batch_dev.h)
+    ba_dbuf<long long> d_ptr;
+    ba_dbuf<double> d_X, d_x, d_K, d_st, d_res;
+    batch_stream bs(opt->device, 6 * (size_t)np);
+    if (bs.rc) return bs.rc;
+    hipStream_t s = bs.s;
+    TRY_RC(d_ptr.alloc((size_t)np + 1));
+    TRY_RC(d_X.alloc(3 * (size_t)N));
+    TRY_RC(d_x.alloc(2 * (size_t)N));
+    TRY_RC(d_K.alloc(4 * (size_t)np));
+    TRY_RC(d_st.alloc((size_t)(na * na + na + 1) * np));   // U | eA | old cost per problem
+    TRY_RC(upload(d_ptr.get(), pr->obs_ptr, (size_t)np + 1, s));
+    TRY_RC(upload(d_X.get(), pr->X, 3 * (size_t)N, s));
+    TRY_RC(upload(d_x.get(), pr->x, 2 * (size_t)N, s));
+    TRY_RC(upload(d_K.get(), pr->K, 4 * (size_t)np, s));
     batch_lm lm((size_t)np, opt);   // the LM control, per problem (ba_batch_lm.h)
-    do {
-        if ((rc = dmalloc_n(&d_ptr, np + 1)) || (rc = dmalloc_n(&d_X, 3 * (size_t)N)) ||
-            (rc = dmalloc_n(&d_x, 2 * (size_t)N)) || (rc = dmalloc_n(&d_K, 4 * (size_t)np)) ||
-            (rc = dmalloc_n(&d_a, (size_t)na * np)) || (rc = dmalloc_n(&d_an, (size_t)na * np)) ||
-            (rc = dmalloc_n(&d_st, (size_t)NUE * np)) || (rc = dmalloc_n(&d_lam, 2 * (size_t)np)) ||
-            (rc = dmalloc_n(&d_out, 4 * (size_t)np)))
-            break;
-        d_fl = d_lam + np;
-        if (hipMemcpyAsync(d_ptr, pr->obs_ptr, sizeof(long long) * (np + 1), hipMemcpyHostToDevice,
-                           s) != hipSuccess ||
-            (N > 0 && (hipMemcpyAsync(d_X, pr->X, sizeof(double) * 3 * N, hipMemcpyHostToDevice,
-                                      s) != hipSuccess ||
-                       hipMemcpyAsync(d_x, pr->x, sizeof(double) * 2 * N, hipMemcpyHostToDevice,
-                                      s) != hipSuccess)) ||
-            hipMemcpyAsync(d_K, pr->K, sizeof(double) * 4 * np, hipMemcpyHostToDevice, s) !=
-                hipSuccess ||
-            hipMemcpyAsync(d_a, a, sizeof(double) * na * np, hipMemcpyHostToDevice, s) !=
-                hipSuccess) {
-            rc = -1;
-            break;
-        }
-        while (lm.stage(h_lam, h_fl)) {
-            if (hipMemcpyAsync(d_lam, h_lam, sizeof(double) * 2 * np, hipMemcpyHostToDevice, s) !=
-                hipSuccess) {
-                rc = -1;
-                break;
-            }
-            if ((rc = rs_launch(na, jacobian == VLGBA_JAC_ANALYTIC,
-                                rs_args{np, d_ptr, d_X, d_x, d_K, d_a, d_an, d_st, d_lam, d_fl,
-                                        d_out, ls},
-                                s)))
-                break;
-            if (hipGetLastError() != hipSuccess ||
-                hipMemcpyAsync(h_out, d_out, sizeof(double) * 4 * np, hipMemcpyDeviceToHost,
-                               s) != hipSuccess ||
-                hipStreamSynchronize(s) != hipSuccess) {
-                rc = -1;
-                break;
-            }
-            lm.apply(h_out, pr->obs_ptr);
-        }
-        if (rc) break;
-        // the last accepted step's parameters
-        std::vector<double> an((size_t)na * np);
-        if (hipMemcpyAsync(a, d_a, sizeof(double) * na * np, hipMemcpyDeviceToHost, s) !=
-                hipSuccess ||
-            hipMemcpyAsync(an.data(), d_an, sizeof(double) * na * np, hipMemcpyDeviceToHost, s) !=
-                hipSuccess ||
-            hipStreamSynchronize(s) != hipSuccess) {
-            rc = -1;
-            break;
-        }
-        for (int q = 0; q < np; q++)
-            if (lm.accepted_prev[q])
-                std::memcpy(a + (size_t)na * q, an.data() + (size_t)na * q, sizeof(double) * na);
-        lm.write_errors(error_out, error_cap, num_error);
-        if (N > 0 && (res_out || w_out)) {   // at the returned parameters
-            if ((rc = dmalloc_n(&d_res, 3 * (size_t)N))) break;
-            if (hipMemcpyAsync(d_a, a, sizeof(double) * na * np, hipMemcpyHostToDevice, s) !=
-                hipSuccess) {
-                rc = -1;
-                break;
-            }
+    const batch_dev_fn pass = [&](const batch_dev_io &d) {
+        return rs_launch(na, jacobian == VLGBA_JAC_ANALYTIC,
+                         rs_args{np, d_ptr, d_X, d_x, d_K, d.x, d.x_new, d_st, d.lam, d.flags,
+                                 d.out, ls},
+                         s);
+    };
+    batch_dev_fn residuals;
+    if (N > 0 && (res_out || w_out))
+        residuals = [&](const batch_dev_io &d) {
+            TRY_RC(d_res.alloc(3 * (size_t)N));
             double *d_w = d_res + 2 * (size_t)N;
-            switch (na) {
-            case 6:
-                k_resect_residuals<6><<<np, 256, 0, s>>>(np, d_ptr, d_X, d_x, d_K, d_a, ls, d_res,
-                                                         d_w);
-                break;
-            case 7:
-                k_resect_residuals<7><<<np, 256, 0, s>>>(np, d_ptr, d_X, d_x, d_K, d_a, ls, d_res,
-                                                         d_w);
-                break;
-            case BA_RAD_NA:
-                k_resect_residuals<BA_RAD_NA><<<np, 256, 0, s>>>(np, d_ptr, d_X, d_x, d_K, d_a, ls,
-                                                                 d_res, d_w);
-                break;
-            default:
-                k_resect_residuals<10><<<np, 256, 0, s>>>(np, d_ptr, d_X, d_x, d_K, d_a, ls, d_res,
-                                                          d_w);
-                break;
-            }
-            if (hipGetLastError() != hipSuccess ||
-                (res_out && hipMemcpyAsync(res_out, d_res, sizeof(double) * 2 * N,
-                                           hipMemcpyDeviceToHost, s) != hipSuccess) ||
-                (w_out && hipMemcpyAsync(w_out, d_w, sizeof(double) * N, hipMemcpyDeviceToHost,
-                                         s) != hipSuccess) ||
-                hipStreamSynchronize(s) != hipSuccess)
-                rc = -1;
-        }
-    } while (0);
-    (void)hipStreamSynchronize(s);
-    for (void *p : {(void *)d_ptr, (void *)d_X, (void *)d_x, (void *)d_K, (void *)d_a,
-                    (void *)d_an, (void *)d_st, (void *)d_lam, (void *)d_out, (void *)d_res})
-        if (p) ba_dfree(p);
-    rs_release(pool);
-    lm.fill_stats(stats, t0);
-    return rc;
+            TRY_RC(rs_dispatch_na(na, [&](auto c) {
+                k_resect_residuals<decltype(c)::value><<<np, 256, 0, s>>>(
+                    np, d_ptr, d_X, d_x, d_K, d.x, ls, d_res, d_w);
+                return -(int)hipGetLastError();
+            }));
+            if (res_out) TRY_RC(download(res_out, d_res.get(), 2 * (size_t)N, s));
+            if (w_out) TRY_RC(download(w_out, d_w, (size_t)N, s));
+            return 0;
+        };
+    return batch_dev_run(bs, lm, na, pr->obs_ptr, a, error_out, error_cap, num_error, stats, t0,
+                         pass, residuals);
 }
 }   // namespace
 

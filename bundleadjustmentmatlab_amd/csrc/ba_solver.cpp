@@ -148,30 +148,8 @@ int ba_ensure_dyn_lds(const void *fn, size_t bytes)
 
 namespace {
 
-template <typename T>
-int dalloc(T **p, size_t count)
-{
-    *p = (T *)ba_dmalloc(sizeof(T) * (count ? count : 1));
-    return *p ? 0 : -(int)hipErrorOutOfMemory;
-}
-
-template <typename T>
-int upload(T *dst, const T *src, size_t count, hipStream_t s)
-{
-    if (count == 0) return 0;
-    hipError_t e = hipMemcpyAsync(dst, src, sizeof(T) * count, hipMemcpyHostToDevice, s);
-    return e == hipSuccess ? 0 : -(int)e;
-}
-
-template <typename T>
-int download(T *dst, const T *src, size_t count, hipStream_t s)
-{
-    if (count == 0) return 0;
-    hipError_t e = hipMemcpyAsync(dst, src, sizeof(T) * count, hipMemcpyDeviceToHost, s);
-    return e == hipSuccess ? 0 : -(int)e;
-}
-
-#define TRY(x)                                                                      \
+// dalloc, upload, download: ba_internal.h
+#define TRY(x)                                                                     \
     do {                                                                            \
         int rc__ = (x);                                                             \
         if (rc__) return rc__;                                                      \

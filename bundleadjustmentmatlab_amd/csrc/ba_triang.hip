@@ -26,16 +26,20 @@
 //
 // Geometry: a wave per workgroup, one lane per point, so that a batch of a few
 // hundred points still spreads over CUs.  The arithmetic is ba_triang_math.h
-// (host and device); the working set of a lane stays in registers.
+// (host and device); the working set of a lane stays in registers.  The LM
+// control is the driver of ba_batch_lm.h on the device backend of
+// ba_batch_dev.h, as in ba_resect.hip: intersect_run checks the arguments,
+// uploads the tracks and hands over a launch and a residual lambda.
 //
 // vlgba_triangulate_ex / vlgba_intersect_ex (include/vlgba.h) add the radial
 // lens (k1, k2 per camera in a side array next to the unchanged records; the
 // undistortion before triangulation.m's rows), the closed-form B and the robust
-// losses: k_triangulate_radial, and k_intersect_pass<true> beside the plain
-// entry's k_intersect_pass<false>, in which the mode folds away.
-#include "ba_batch_lm.h"
-#include "ba_internal.h"
+// losses: k_triangulate<true>, and k_intersect_pass<true>, beside the plain
+// entries' <false>, in which the mode folds away.
+#include "ba_batch_dev.h"
 #include "ba_triang_math.h"
+
+#include <cstring>
 
 #define TRI_WAVE 64
 
@@ -58,30 +62,10 @@ __global__ __launch_bounds__(TRI_WAVE) void k_tri_cameras(int m, const double *_
     for (int c = 0; c < TRI_CAM; c++) rec[(size_t)TRI_CAM * j + c] = r[c];
 }
 
-__global__ __launch_bounds__(TRI_WAVE) void k_triangulate(long long n,
-                                                          const long long *__restrict__ obs_ptr,
-                                                          const int *__restrict__ obs_cam,
-                                                          const double *__restrict__ obs_x,
-                                                          const double *__restrict__ rec,
-                                                          double *__restrict__ X,
-                                                          int *__restrict__ status)
-{
-    const long long i = (long long)blockIdx.x * TRI_WAVE + threadIdx.x;
-    if (i >= n) return;
-    const long long o0 = obs_ptr[i], nv = obs_ptr[i + 1] - o0;
-    double x[4];
-    const int st = tri_point(nv, obs_cam + o0, obs_x + 2 * o0, rec, x);
-    X[4 * i] = x[0];
-    X[4 * i + 1] = x[1];
-    X[4 * i + 2] = x[2];
-    X[4 * i + 3] = x[3];
-    status[i] = st;
-}
-
-// ---- the entries with a mode (vlgba_triangulate_ex, vlgba_intersect_ex) -------
-// k_triangulate under radial lenses: every measurement undistorted first
-// (tri_point_radial)
-__global__ __launch_bounds__(TRI_WAVE) void k_triangulate_radial(
+// RADIAL = false: vlgba_triangulate's kernel (kd is not read); true: radial
+// lenses, every measurement undistorted first (tri_point<true>)
+template <bool RADIAL>
+__global__ __launch_bounds__(TRI_WAVE) void k_triangulate(
     long long n, const long long *__restrict__ obs_ptr, const int *__restrict__ obs_cam,
     const double *__restrict__ obs_x, const double *__restrict__ rec,
     const double *__restrict__ kd, double *__restrict__ X, int *__restrict__ status)
@@ -90,7 +74,7 @@ __global__ __launch_bounds__(TRI_WAVE) void k_triangulate_radial(
     if (i >= n) return;
     const long long o0 = obs_ptr[i], nv = obs_ptr[i + 1] - o0;
     double x[4];
-    const int st = tri_point_radial(nv, obs_cam + o0, obs_x + 2 * o0, rec, kd, x);
+    const int st = tri_point<RADIAL>(nv, obs_cam + o0, obs_x + 2 * o0, rec, kd, x);
     X[4 * i] = x[0];
     X[4 * i + 1] = x[1];
     X[4 * i + 2] = x[2];
@@ -98,9 +82,7 @@ __global__ __launch_bounds__(TRI_WAVE) void k_triangulate_radial(
     status[i] = st;
 }
 
-// state per point (SoA, entry k of point i at state[k * n + i]): V | eB | old
-// cost, kept across rejected passes (bundle_euclid.m:139 recomputes an identical
-// linearisation, Q12), as k_resect_pass keeps U | eA | old cost.  M = false:
+// One lane per point runs isect_pass_point (ba_triang_math.h).  M = false:
 // vlgba_intersect's pass (md is not read); M = true: the mode md of
 // vlgba_intersect_ex, wave-uniform (the radial projection, the closed-form B,
 // the loss: the robust cost in place of the SSE)
@@ -113,37 +95,12 @@ __global__ __launch_bounds__(TRI_WAVE) void k_intersect_pass(
 {
     const long long i = (long long)blockIdx.x * TRI_WAVE + threadIdx.x;
     if (i >= n) return;
-    // staged with lambda as doubles (one copy a pass); a vector load at device
+    // staged with lambda as doubles (one copy a pass); vector loads at device
     // scope, as every per-pass word (ba_internal.h)
     const int fl = (int)__hip_atomic_load(flags + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     if (!(fl & 1)) return;                          // point finished (or without views)
-    const long long o0 = obs_ptr[i], nv = obs_ptr[i + 1] - o0;
-    const int *cam = obs_cam + o0;
-    const double *x = obs_x + 2 * o0;
-    double bv[3], st[TRI_NST];
-    if (fl & 4) {
-#pragma unroll
-        for (int c = 0; c < 3; c++) b[3 * i + c] = b_new[3 * i + c];
-    }
-#pragma unroll
-    for (int c = 0; c < 3; c++) bv[c] = b[3 * i + c];
-    if (fl & 2) {
-        isect_linearize<M>(nv, cam, x, rec, &md, bv, st);
-#pragma unroll
-        for (int k = 0; k < TRI_NST; k++) state[(size_t)k * n + i] = st[k];
-    } else {
-#pragma unroll
-        for (int k = 0; k < TRI_NST; k++) st[k] = state[(size_t)k * n + i];
-    }
     const double lambda = __hip_atomic_load(lam_p + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    double bn[3], nsum, g;
-    isect_step<M>(nv, cam, x, rec, &md, bv, st, lambda, bn, &nsum, &g);
-#pragma unroll
-    for (int c = 0; c < 3; c++) b_new[3 * i + c] = bn[c];
-    out[4 * i + 0] = st[12];
-    out[4 * i + 1] = nsum;
-    out[4 * i + 2] = g;
-    out[4 * i + 3] = 0.0;
+    isect_pass_point<M>(i, n, obs_ptr, obs_cam, obs_x, rec, &md, b, b_new, state, fl, lambda, out);
 }
 
 // res_out / w_out of vlgba_intersect_ex at the returned points b; either may
@@ -161,14 +118,8 @@ __global__ __launch_bounds__(TRI_WAVE) void k_intersect_residuals(
                       w ? w + o0 : nullptr);
 }
 
-namespace {
-template <typename T>
-int dmalloc_n(T **p, size_t n)
-{
-    *p = (T *)ba_dmalloc(sizeof(T) * (n ? n : 1));
-    return *p ? 0 : -(int)hipErrorOutOfMemory;
-}
 
+namespace {
 // the argument rules both entries share, before any device work
 int check_tracks(int m, const double *K, const double *T, const double *w, long long n,
                  const long long *obs_ptr, const int *obs_cam, const double *obs_x,
@@ -187,51 +138,37 @@ int check_tracks(int m, const double *K, const double *T, const double *w, long 
 
 // device copies of the cameras' records and the tracks
 struct tri_dev {
-    long long *ptr = nullptr;
-    int *cam = nullptr;
-    double *x = nullptr, *in = nullptr, *rec = nullptr;
+    ba_dbuf<long long> ptr;
+    ba_dbuf<int> cam;
+    ba_dbuf<double> x, in, rec;
     double *kd = nullptr;   // k1, k2 per camera (in + 10 m) or null: pinhole
-    ~tri_dev()
+    int load(int m, const double *K, const double *T, const double *w, long long n,
+             const long long *obs_ptr, const int *obs_cam, const double *obs_x, hipStream_t s,
+             const double *kd_host)
     {
-        for (void *p : {(void *)ptr, (void *)cam, (void *)x, (void *)in, (void *)rec})
-            if (p) ba_dfree(p);
-    }
-    int upload(int m, const double *K, const double *T, const double *w, long long n,
-               const long long *obs_ptr, const int *obs_cam, const double *obs_x, hipStream_t s,
-               const double *kd_host = nullptr)
-    {
-        const long long N = obs_ptr[n];
-        int rc;
-        if ((rc = dmalloc_n(&ptr, (size_t)n + 1)) || (rc = dmalloc_n(&cam, (size_t)N)) ||
-            (rc = dmalloc_n(&x, 2 * (size_t)N)) || (rc = dmalloc_n(&in, 12 * (size_t)m)) ||
-            (rc = dmalloc_n(&rec, (size_t)TRI_CAM * m)))
-            return rc;
-        if (hipMemcpyAsync(ptr, obs_ptr, sizeof(long long) * (n + 1), hipMemcpyHostToDevice, s) !=
-                hipSuccess ||
-            (N > 0 && (hipMemcpyAsync(cam, obs_cam, sizeof(int) * N, hipMemcpyHostToDevice, s) !=
-                           hipSuccess ||
-                       hipMemcpyAsync(x, obs_x, sizeof(double) * 2 * N, hipMemcpyHostToDevice,
-                                      s) != hipSuccess)) ||
-            hipMemcpyAsync(in, K, sizeof(double) * 4 * m, hipMemcpyHostToDevice, s) !=
-                hipSuccess ||
-            hipMemcpyAsync(in + 4 * (size_t)m, T, sizeof(double) * 3 * m, hipMemcpyHostToDevice,
-                           s) != hipSuccess ||
-            hipMemcpyAsync(in + 7 * (size_t)m, w, sizeof(double) * 3 * m, hipMemcpyHostToDevice,
-                           s) != hipSuccess)
-            return -1;
+        const size_t N = (size_t)obs_ptr[n], M = (size_t)m;
+        TRY_RC(ptr.alloc((size_t)n + 1));
+        TRY_RC(cam.alloc(N));
+        TRY_RC(x.alloc(2 * N));
+        TRY_RC(in.alloc(12 * M));
+        TRY_RC(rec.alloc(TRI_CAM * M));
+        TRY_RC(upload(ptr.get(), obs_ptr, (size_t)n + 1, s));
+        TRY_RC(upload(cam.get(), obs_cam, N, s));
+        TRY_RC(upload(x.get(), obs_x, 2 * N, s));
+        TRY_RC(upload(in.get(), K, 4 * M, s));
+        TRY_RC(upload(in + 4 * M, T, 3 * M, s));
+        TRY_RC(upload(in + 7 * M, w, 3 * M, s));
         if (kd_host) {
-            kd = in + 10 * (size_t)m;
-            if (hipMemcpyAsync(kd, kd_host, sizeof(double) * 2 * m, hipMemcpyHostToDevice, s) !=
-                hipSuccess)
-                return -1;
+            kd = in + 10 * M;
+            TRY_RC(upload(kd, kd_host, 2 * M, s));
         }
         k_tri_cameras<<<(m + TRI_WAVE - 1) / TRI_WAVE, TRI_WAVE, 0, s>>>(
-            m, in, in + 4 * (size_t)m, in + 7 * (size_t)m, kd_host != nullptr, rec);
-        return hipGetLastError() == hipSuccess ? 0 : -1;
+            m, in, in + 4 * M, in + 7 * M, kd_host != nullptr, rec);
+        return -(int)hipGetLastError();
     }
 };
 
-// vlgba_triangulate (kd null: k_triangulate) and vlgba_triangulate_ex
+// vlgba_triangulate (kd null: k_triangulate<false>) and vlgba_triangulate_ex
 int triangulate_run(int m, const double *K, const double *T, const double *w, const double *kd,
                     long long n, const long long *obs_ptr, const int *obs_cam,
                     const double *obs_x, int device, double *X, int *status)
@@ -240,41 +177,24 @@ int triangulate_run(int m, const double *K, const double *T, const double *w, co
     if (n == 0) return 0;
     if ((n + TRI_WAVE - 1) / TRI_WAVE > 0x7fffffffLL) return VLGBA_E_ARG;
     VLGBA_CHECK(hipSetDevice(device));
-    rs_pool pool{device, nullptr, nullptr, 0};
-    if (rs_acquire(device, 0, pool)) {
-        if (pool.s) rs_release(pool);
-        return -1;
-    }
-    hipStream_t s = pool.s;
-    int rc = 0;
-    {
-        tri_dev d;
-        double *d_X = nullptr;
-        int *d_st = nullptr;
-        const unsigned grid = (unsigned)((n + TRI_WAVE - 1) / TRI_WAVE);
-        do {
-            if ((rc = d.upload(m, K, T, w, n, obs_ptr, obs_cam, obs_x, s, kd)) ||
-                (rc = dmalloc_n(&d_X, 4 * (size_t)n)) || (rc = dmalloc_n(&d_st, (size_t)n)))
-                break;
-            if (kd)
-                k_triangulate_radial<<<grid, TRI_WAVE, 0, s>>>(n, d.ptr, d.cam, d.x, d.rec, d.kd,
-                                                               d_X, d_st);
-            else
-                k_triangulate<<<grid, TRI_WAVE, 0, s>>>(n, d.ptr, d.cam, d.x, d.rec, d_X, d_st);
-            if (hipGetLastError() != hipSuccess ||
-                hipMemcpyAsync(X, d_X, sizeof(double) * 4 * n, hipMemcpyDeviceToHost, s) !=
-                    hipSuccess ||
-                (status && hipMemcpyAsync(status, d_st, sizeof(int) * n, hipMemcpyDeviceToHost,
-                                          s) != hipSuccess) ||
-                hipStreamSynchronize(s) != hipSuccess)
-                rc = -1;
-        } while (0);
-        (void)hipStreamSynchronize(s);
-        if (d_X) ba_dfree(d_X);
-        if (d_st) ba_dfree(d_st);
-    }
-    rs_release(pool);
-    return rc;
+    // before the stream's guard: freed after it has drained (ba_batch_dev.h)
+    tri_dev d;
+    ba_dbuf<double> d_X;
+    ba_dbuf<int> d_st;
+    batch_stream bs(device, 0);
+    if (bs.rc) return bs.rc;
+    hipStream_t s = bs.s;
+    const unsigned grid = (unsigned)((n + TRI_WAVE - 1) / TRI_WAVE);
+    TRY_RC(d.load(m, K, T, w, n, obs_ptr, obs_cam, obs_x, s, kd));
+    TRY_RC(d_X.alloc(4 * (size_t)n));
+    TRY_RC(d_st.alloc((size_t)n));
+    const auto kern = kd ? k_triangulate<true> : k_triangulate<false>;
+    kern<<<grid, TRI_WAVE, 0, s>>>(n, d.ptr, d.cam, d.x, d.rec, d.kd, d_X, d_st);
+    VLGBA_CHECK(hipGetLastError());
+    TRY_RC(download(X, d_X.get(), 4 * (size_t)n, s));
+    if (status) TRY_RC(download(status, d_st.get(), (size_t)n, s));
+    VLGBA_CHECK(hipStreamSynchronize(s));
+    return 0;
 }
 
 // vlgba_intersect (md null: k_intersect_pass<false>) and vlgba_intersect_ex
@@ -294,101 +214,43 @@ int intersect_run(int m, const double *K, const double *T, const double *w, long
     if (!opt) opt = &dflt;
     VLGBA_CHECK(hipSetDevice(opt->device));
     const auto t0 = std::chrono::steady_clock::now();
-    rs_pool pool{opt->device, nullptr, nullptr, 0};
-    if (rs_acquire(opt->device, 6 * (size_t)n, pool)) {
-        if (pool.s) rs_release(pool);
-        return -1;
-    }
-    hipStream_t s = pool.s;
-    double *h_lam = pool.pin, *h_fl = pool.pin + n, *h_out = pool.pin + 2 * (size_t)n;
+    // before the stream's guard: freed after it has drained (ba_batch_dev.h)
+    tri_dev d;
+    ba_dbuf<double> d_st, d_res;
+    batch_stream bs(opt->device, 6 * (size_t)n);
+    if (bs.rc) return bs.rc;
+    hipStream_t s = bs.s;
     batch_lm lm((size_t)n, opt);   // the LM control, per point (ba_batch_lm.h)
     for (long long i = 0; i < n; i++)   // a point with no views is left untouched
         if (obs_ptr[i + 1] == obs_ptr[i]) lm.active[i] = 0;
-    const long long N = obs_ptr[n];
-    int rc = 0;
-    {
-        tri_dev d;
-        double *d_b = nullptr, *d_bn = nullptr, *d_st = nullptr, *d_lam = nullptr,
-               *d_out = nullptr, *d_res = nullptr;
-        const unsigned grid = (unsigned)((n + TRI_WAVE - 1) / TRI_WAVE);
-        do {
-            if ((rc = d.upload(m, K, T, w, n, obs_ptr, obs_cam, obs_x, s, md ? md->kd : nullptr)) ||
-                (rc = dmalloc_n(&d_b, 3 * (size_t)n)) || (rc = dmalloc_n(&d_bn, 3 * (size_t)n)) ||
-                (rc = dmalloc_n(&d_st, (size_t)TRI_NST * n)) ||
-                (rc = dmalloc_n(&d_lam, 2 * (size_t)n)) || (rc = dmalloc_n(&d_out, 4 * (size_t)n)))
-                break;
-            if (hipMemcpyAsync(d_b, X, sizeof(double) * 3 * n, hipMemcpyHostToDevice, s) !=
-                hipSuccess) {
-                rc = -1;
-                break;
-            }
-            isect_mode dm{nullptr, 0, 0, 0.0};
-            if (md) {
-                dm = *md;
-                dm.kd = d.kd;   // the device copy
-            }
-            while (lm.stage(h_lam, h_fl)) {
-                if (hipMemcpyAsync(d_lam, h_lam, sizeof(double) * 2 * n, hipMemcpyHostToDevice,
-                                   s) != hipSuccess) {
-                    rc = -1;
-                    break;
-                }
-                if (md)
-                    k_intersect_pass<true><<<grid, TRI_WAVE, 0, s>>>(
-                        n, d.ptr, d.cam, d.x, d.rec, dm, d_b, d_bn, d_st, d_lam, d_lam + n, d_out);
-                else
-                    k_intersect_pass<false><<<grid, TRI_WAVE, 0, s>>>(
-                        n, d.ptr, d.cam, d.x, d.rec, dm, d_b, d_bn, d_st, d_lam, d_lam + n, d_out);
-                if (hipGetLastError() != hipSuccess ||
-                    hipMemcpyAsync(h_out, d_out, sizeof(double) * 4 * n, hipMemcpyDeviceToHost,
-                                   s) != hipSuccess ||
-                    hipStreamSynchronize(s) != hipSuccess) {
-                    rc = -1;
-                    break;
-                }
-                lm.apply(h_out, obs_ptr);
-            }
-            if (rc) break;
-            // the last accepted step's parameters
-            std::vector<double> bn(3 * (size_t)n);
-            if (hipMemcpyAsync(X, d_b, sizeof(double) * 3 * n, hipMemcpyDeviceToHost, s) !=
-                    hipSuccess ||
-                hipMemcpyAsync(bn.data(), d_bn, sizeof(double) * 3 * n, hipMemcpyDeviceToHost,
-                               s) != hipSuccess ||
-                hipStreamSynchronize(s) != hipSuccess) {
-                rc = -1;
-                break;
-            }
-            for (long long i = 0; i < n; i++)
-                if (lm.accepted_prev[i])
-                    std::memcpy(X + 3 * i, bn.data() + 3 * i, sizeof(double) * 3);
-            lm.write_errors(error_out, error_cap, num_error);
-            if (md && N > 0 && (res_out || w_out)) {   // at the returned points
-                if ((rc = dmalloc_n(&d_res, 3 * (size_t)N))) break;
-                if (hipMemcpyAsync(d_b, X, sizeof(double) * 3 * n, hipMemcpyHostToDevice, s) !=
-                    hipSuccess) {
-                    rc = -1;
-                    break;
-                }
-                k_intersect_residuals<<<grid, TRI_WAVE, 0, s>>>(n, d.ptr, d.cam, d.x, d.rec, dm, d_b,
-                                                                d_res, d_res + 2 * (size_t)N);
-                if (hipGetLastError() != hipSuccess ||
-                    (res_out && hipMemcpyAsync(res_out, d_res, sizeof(double) * 2 * N,
-                                               hipMemcpyDeviceToHost, s) != hipSuccess) ||
-                    (w_out && hipMemcpyAsync(w_out, d_res + 2 * (size_t)N, sizeof(double) * N,
-                                             hipMemcpyDeviceToHost, s) != hipSuccess) ||
-                    hipStreamSynchronize(s) != hipSuccess)
-                    rc = -1;
-            }
-        } while (0);
-        (void)hipStreamSynchronize(s);
-        for (void *p : {(void *)d_b, (void *)d_bn, (void *)d_st, (void *)d_lam, (void *)d_out,
-                        (void *)d_res})
-            if (p) ba_dfree(p);
+    const size_t N = (size_t)obs_ptr[n];
+    const unsigned grid = (unsigned)((n + TRI_WAVE - 1) / TRI_WAVE);
+    TRY_RC(d.load(m, K, T, w, n, obs_ptr, obs_cam, obs_x, s, md ? md->kd : nullptr));
+    TRY_RC(d_st.alloc((size_t)TRI_NST * n));
+    isect_mode dm{nullptr, 0, 0, 0.0};
+    if (md) {
+        dm = *md;
+        dm.kd = d.kd;   // the device copy
     }
-    rs_release(pool);
-    lm.fill_stats(stats, t0);
-    return rc;
+    const auto kern = md ? k_intersect_pass<true> : k_intersect_pass<false>;
+    const batch_dev_fn pass = [&](const batch_dev_io &p) {
+        kern<<<grid, TRI_WAVE, 0, s>>>(n, d.ptr, d.cam, d.x, d.rec, dm, p.x, p.x_new, d_st, p.lam,
+                                       p.flags, p.out);
+        return 0;
+    };
+    batch_dev_fn residuals;
+    if (md && N > 0 && (res_out || w_out))
+        residuals = [&](const batch_dev_io &p) {
+            TRY_RC(d_res.alloc(3 * N));
+            k_intersect_residuals<<<grid, TRI_WAVE, 0, s>>>(n, d.ptr, d.cam, d.x, d.rec, dm, p.x,
+                                                            d_res, d_res + 2 * N);
+            VLGBA_CHECK(hipGetLastError());
+            if (res_out) TRY_RC(download(res_out, d_res.get(), 2 * N, s));
+            if (w_out) TRY_RC(download(w_out, d_res + 2 * N, N, s));
+            return 0;
+        };
+    return batch_dev_run(bs, lm, 3, obs_ptr, X, error_out, error_cap, num_error, stats, t0, pass,
+                         residuals);
 }
 }   // namespace
 
@@ -430,4 +292,3 @@ extern "C" int vlgba_intersect_ex(int m, const double *K, const double *T, const
     return intersect_run(m, K, T, w, n, obs_ptr, obs_cam, obs_x, opt, &md, X, error_out,
                          error_cap, num_error, res_out, w_out, stats);
 }
-

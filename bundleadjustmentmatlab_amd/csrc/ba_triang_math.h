@@ -1,8 +1,8 @@
 /*
  * ba_triang_math.h -- the per-point arithmetic of ba_triang.hip (linear
  * triangulation and the one-point LM pass with the motion fixed), host and
- * device: the kernels are thin loops around these, and a CPU build can run the
- * same code.  Include from C++ or HIP.
+ * device: the kernels are thin loops around these, and tests/native/
+ * block_host.cpp runs the same code on the CPU.  Include from C++ or HIP.
  *
  * Camera records (k_tri_cameras writes them once per call):
  *   TRI_CAM doubles per camera:  P (12, 3 x 4 column major:
@@ -156,7 +156,17 @@ VLG_HD void tri_smallest_vec(const double G[10], double v[4])
 VLG_HD int tri_solve(const double G[10], long long nv, const int *cam, const double *rec,
                      double X[4]);
 
-VLG_HD int tri_point(long long nv, const int *cam, const double *x, const double *rec, double X[4])
+VLG_HD int tri_undistort(double f, const double c[2], double k1, double k2, const double x[2],
+                         double n[2]);
+
+/* RADIAL = false: kd is not read.  RADIAL = true, radial lenses (kd: k1, k2 per
+ * camera; f = K4[0], the principal point K4[2], K4[3] of the record, whose P
+ * was formed with K = (f, f, cx, cy)): every measurement is undistorted to the
+ * pinhole pixel f n + c first, then the rows are the same.  A view that
+ * tri_undistort fails gives the point status 2 and zeros. */
+template <bool RADIAL>
+VLG_HD int tri_point(long long nv, const int *cam, const double *x, const double *rec,
+                     const double *kd, double X[4])
 {
     double G[10];
     long long o;
@@ -164,8 +174,19 @@ VLG_HD int tri_point(long long nv, const int *cam, const double *x, const double
     X[0] = X[1] = X[2] = X[3] = 0.0;
     if (nv < 2) return 2;
     for (c = 0; c < 10; c++) G[c] = 0.0;
-    for (o = 0; o < nv; o++)
-        tri_add_view(G, rec + (size_t)TRI_CAM * cam[o], x[2 * o], x[2 * o + 1]);
+    for (o = 0; o < nv; o++) {
+        const double *rc = rec + (size_t)TRI_CAM * cam[o];
+        if (RADIAL) {
+            const double *k4 = rc + TRI_CAM_K4;
+            double n[2];
+            if (!tri_undistort(k4[0], k4 + 2, kd[2 * (size_t)cam[o]], kd[2 * (size_t)cam[o] + 1],
+                               x + 2 * o, n))
+                return 2;
+            tri_add_view(G, rc, k4[0] * n[0] + k4[2], k4[0] * n[1] + k4[3]);
+        } else {
+            tri_add_view(G, rc, x[2 * o], x[2 * o + 1]);
+        }
+    }
     return tri_solve(G, nv, cam, rec, X);
 }
 
@@ -206,32 +227,6 @@ VLG_HD int tri_undistort(double f, const double c[2], double k1, double k2, cons
     n[0] = nd0 * (r / rd);
     n[1] = nd1 * (r / rd);
     return 1;
-}
-
-/* tri_point under radial lenses (kd: k1, k2 per camera; f = K4[0], the
- * principal point K4[2], K4[3] of the record, whose P was formed with K =
- * (f, f, cx, cy)): every measurement is undistorted to the pinhole pixel
- * f n + c first, then the rows are tri_point's.  A view that tri_undistort
- * fails gives the point status 2 and zeros. */
-VLG_HD int tri_point_radial(long long nv, const int *cam, const double *x, const double *rec,
-                            const double *kd, double X[4])
-{
-    double G[10];
-    long long o;
-    int c;
-    X[0] = X[1] = X[2] = X[3] = 0.0;
-    if (nv < 2) return 2;
-    for (c = 0; c < 10; c++) G[c] = 0.0;
-    for (o = 0; o < nv; o++) {
-        const double *rc = rec + (size_t)TRI_CAM * cam[o];
-        const double *k4 = rc + TRI_CAM_K4;
-        double n[2];
-        if (!tri_undistort(k4[0], k4 + 2, kd[2 * (size_t)cam[o]], kd[2 * (size_t)cam[o] + 1],
-                           x + 2 * o, n))
-            return 2;
-        tri_add_view(G, rc, k4[0] * n[0] + k4[2], k4[0] * n[1] + k4[3]);
-    }
-    return tri_solve(G, nv, cam, rec, X);
 }
 
 /* the point from the Gram matrix of its rows: X (zeros unless status 1) */
@@ -417,6 +412,41 @@ VLG_HD void isect_step(long long nv, const int *cam, const double *x, const doub
     for (r = 0; r < 3; r++) g = g + db[r] * (lambda * db[r] + st[9 + r]);
     *new_cost = ns;
     *dpg = g;
+}
+
+/* One LM pass of point i of n (the protocol of ba_batch_lm.h; k_intersect_pass's
+ * lane and the host loop of tests/native/block_host.cpp): fl and lambda are the
+ * point's flags word and lambda of this pass, b / b_new its two parameter sets
+ * (3 n each), state (SoA, entry k of point i at state[k * n + i]) V | eB | old
+ * cost, kept across rejected passes (bundle_euclid.m:139 recomputes an
+ * identical linearisation, Q12), out the four scalars per point. */
+template <bool M>
+VLG_HD void isect_pass_point(long long i, long long n, const long long *obs_ptr,
+                             const int *obs_cam, const double *obs_x, const double *rec,
+                             const isect_mode *md, double *b, double *b_new, double *state,
+                             int fl, double lambda, double *out)
+{
+    if (!(fl & 1)) return;   /* point finished (or without views) */
+    const long long o0 = obs_ptr[i], nv = obs_ptr[i + 1] - o0;
+    const int *cam = obs_cam + o0;
+    const double *x = obs_x + 2 * o0;
+    double bv[3], st[TRI_NST], bn[3], nsum, g;
+    int c, k;
+    if (fl & 4)              /* the previous pass was accepted */
+        for (c = 0; c < 3; c++) b[3 * i + c] = b_new[3 * i + c];
+    for (c = 0; c < 3; c++) bv[c] = b[3 * i + c];
+    if (fl & 2) {
+        isect_linearize<M>(nv, cam, x, rec, md, bv, st);
+        for (k = 0; k < TRI_NST; k++) state[(size_t)k * n + i] = st[k];
+    } else {
+        for (k = 0; k < TRI_NST; k++) st[k] = state[(size_t)k * n + i];
+    }
+    isect_step<M>(nv, cam, x, rec, md, bv, st, lambda, bn, &nsum, &g);
+    for (c = 0; c < 3; c++) b_new[3 * i + c] = bn[c];
+    out[4 * i + 0] = st[12];
+    out[4 * i + 1] = nsum;
+    out[4 * i + 2] = g;
+    out[4 * i + 3] = 0.0;   /* no pinv fallback: vlg_pinv3 is the solve */
 }
 
 /* the unweighted residuals x - x_hat (2 per view) and the loss's weights (1 per

@@ -543,7 +543,10 @@ typedef struct {
 /* a (num_a x nprob, [w; T; (K)] per camera) is the start point and receives the
  * result; error_out (nprob x error_cap, row q = camera q's error_) and
  * num_error (nprob) may be NULL.  opt: max_iter, max_iter2, lambda0,
- * stop_rel, device are honoured (the rest does not apply). */
+ * stop_rel, device are honoured (the rest does not apply).  stats (may be
+ * NULL): iterations / accepted summed over the cameras, camera 0's lambda,
+ * pinv_passes the camera passes whose num_a x num_a Cholesky met a pivot that
+ * was not positive. */
 int vlgba_resect(const vlgba_resect_problem *prob, const vlgba_options *opt, double *a,
                  double *error_out, int error_cap, int *num_error, vlgba_stats *stats);
 
