@@ -150,6 +150,10 @@ SIGNATURES = {
     "vlgba_debug_force_status": (c_int, [ctypes.c_void_p, c_int, c_int]),
     "vlgba_debug_nd_plan": (c_int, [c_int, c_int, c_ip, c_int, c_ip, c_ip]),
     "vlgba_debug_selinv_plan": (c_int, [c_int, c_ip, c_ip, c_ip]),
+    "vlgba_debug_pcg_plan": (c_int, [c_int, c_ip, c_int, c_ip, c_ip]),
+    "vlgba_set_pcg": (c_int, [ctypes.c_void_p, c_double, c_int]),
+    "vlgba_get_pcg": (c_int, [ctypes.c_void_p, c_dp, c_ip]),
+    "vlgba_get_pcg_stats": (c_int, [ctypes.c_void_p, c_ip, c_dp, c_ip, ctypes.POINTER(c_ll)]),
 }
 
 ERRORS = {-1001: "bad argument",

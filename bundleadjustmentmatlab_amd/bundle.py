@@ -209,7 +209,11 @@ class BundleAdjuster:
     picks the reduced-camera solve: "auto" (cyclic reduction when S is
     tile-tridiagonal, else envelope Cholesky -- on a nested-dissection camera
     order when that shortens its chain of steps), "envelope", "nd" (the
-    nested-dissection order whenever the cameras split) or "dense";
+    nested-dissection order whenever the cameras split), "dense", or "pcg":
+    block-Jacobi preconditioned conjugate gradients on the co-visible blocks
+    (opt-in; an inexact step, no dense S -- device memory linear in the blocks
+    and cameras; ``pcg_tol`` / ``pcg_max_iter``: set_pcg, defaults 0.1 and 500;
+    not with ``parity`` / ``ordered``: VlgbaError -1001).
     ``dense_solve=True`` is the same as solver="dense".  ``schur_kernel``
     picks the fast-path Schur complement kernel: "auto" (dense per-chunk
     products on fp64 MFMA when the tracks fit) or "terms" (per-term sums).
@@ -236,7 +240,8 @@ class BundleAdjuster:
     problem that the planner hands to the ordered kernels all the same
     (plan_info()["ordered"] == 1) "analytic" raises VlgbaError -1001.
     """
-    SOLVERS = {"auto": 0, "dense": 1, "envelope": 2, "sequential": 3, "nd": 4}
+    SOLVERS = {"auto": 0, "dense": 1, "envelope": 2, "sequential": 3, "nd": 4,
+               "pcg": 5}
     SCHUR_KERNELS = {"auto": 0, "terms": 1}
     SEMANTICS = {"mex": 0, "nomex": 1}
     MODELS = {"euclidean": MODEL_EUCLIDEAN, "projective": MODEL_PROJECTIVE}
@@ -247,7 +252,7 @@ class BundleAdjuster:
                  dense_solve=False, ordered=False, allreduce=None, solver=None,
                  schur_kernel="auto", semantics="mex", model="euclidean", m=None,
                  parity=False, stop_rel=0.0, log=None, loss="none", loss_scale=0.0,
-                 jacobian=None):
+                 jacobian=None, pcg_tol=None, pcg_max_iter=None):
         L = lib()
         if jacobian is not None and jacobian not in JACOBIANS:
             raise ValueError(f"jacobian must be one of {sorted(JACOBIANS)}")
@@ -316,6 +321,8 @@ class BundleAdjuster:
                 self.set_loss(loss, loss_scale)
             if jacobian is not None and self.get_jacobian() != jacobian:
                 self.set_jacobian(jacobian)       # (over the environment's default)
+            if pcg_tol is not None or pcg_max_iter is not None:
+                self.set_pcg(pcg_tol, pcg_max_iter)
         except Exception:
             self.close()
             raise
@@ -347,6 +354,32 @@ class BundleAdjuster:
         kind = ctypes.c_int()
         check(self._L.vlgba_get_jacobian(self._h, ctypes.byref(kind)), "vlgba_get_jacobian")
         return {v: k for k, v in JACOBIANS.items()}[kind.value]
+
+    def set_pcg(self, tol=None, max_iter=None):
+        """The stop rule of a solver="pcg" context from here on (vlgba_set_pcg):
+        the relative residual sqrt(r'M^-1 r / e_'M^-1 e_) to reach (0 < tol < 1)
+        and the iteration limit; None keeps the current value."""
+        check(self._L.vlgba_set_pcg(self._h, 0.0 if tol is None else float(tol),
+                                    0 if max_iter is None else int(max_iter)), "vlgba_set_pcg")
+
+    def get_pcg(self):
+        """(tol, max_iter) of a solver="pcg" context (vlgba_get_pcg)."""
+        tol, it = ctypes.c_double(), ctypes.c_int()
+        check(self._L.vlgba_get_pcg(self._h, ctypes.byref(tol), ctypes.byref(it)),
+              "vlgba_get_pcg")
+        return tol.value, it.value
+
+    def pcg_stats(self):
+        """The last pass's PCG solve (vlgba_get_pcg_stats): dict of iterations,
+        relres (the recurrence's sqrt(rz_k / rz_0) at its end), converged (the
+        tolerance was met; False: the iteration limit ended the solve and the
+        iterate was the step) and total (iterations over the context's passes)."""
+        it, conv, rel, tot = ctypes.c_int(), ctypes.c_int(), ctypes.c_double(), ctypes.c_longlong()
+        check(self._L.vlgba_get_pcg_stats(self._h, ctypes.byref(it), ctypes.byref(rel),
+                                          ctypes.byref(conv), ctypes.byref(tot)),
+              "vlgba_get_pcg_stats")
+        return dict(iterations=it.value, relres=rel.value, converged=bool(conv.value),
+                    total=tot.value)
 
     def residuals(self):
         """Per observation at the current parameters (vlgba_get_residuals), in
@@ -556,7 +589,8 @@ class BundleAdjuster:
                  "tiles", "cr_levels", "cr_elim", "cr_keep", "ordered", "schur_terms",
                  "blob_words", "mfma", "cr_rows", "mfma_groups", "reordered", "long_points",
                  "nd_arcs", "nd_sep_tiles", "solve_flops_factor", "solve_flops_syrk",
-                 "solve_flops_back", "env_runner_runs", "vinv_fold", "camupd_fold")
+                 "solve_flops_back", "env_runner_runs", "vinv_fold", "camupd_fold", "pcg",
+                 "solve_bytes")
 
     def plan_info(self):
         """Execution-plan sizes of this rank (vlgba_plan_info)."""

@@ -66,4 +66,5 @@ struct ba_chol {
     int runner_runs;          // runner launches made (vlgba_plan_info [28])
     int debug_runner_fail;    // the next starts fail (vlgba_debug_force_status word 6)
     hipStream_t rstream;      // the runner's stream (the process's, highest priority)
+    long long bytes;          // device memory ba_chol_setup allocated (vlgba_plan_info [32])
 };

@@ -2283,11 +2283,14 @@ int ba_pinv_apply(ba_dev *d, const double *V, const double *ev, long long ld, co
 }
 
 // ===========================================================================
+// (counted in c->bytes: vlgba_plan_info [32])
 template <typename T>
-static int dev_alloc(T **p, size_t bytes)
+static int dev_alloc(ba_chol *c, T **p, size_t bytes)
 {
     *p = (T *)ba_dmalloc(bytes);
-    return *p ? 0 : -(int)hipErrorOutOfMemory;
+    if (!*p) return -(int)hipErrorOutOfMemory;
+    c->bytes += (long long)bytes;
+    return 0;
 }
 
 // ---- the solve's setup: plan on the host (ba_chol_plan.cpp), allocate, upload
@@ -2318,30 +2321,30 @@ int ba_chol_setup(ba_dev *d, const int *blk_jk, int nb)
     if (P.cr_nlev > 0) {   // cyclic reduction: its records, L(p, e) | L(q, e)
         const int ntc = P.cr_tiles();
         if (P.cr32) {
-            TRY_RC(dev_alloc(&c->xgran, sizeof(unsigned long long) * 64 * (size_t)ntc));
+            TRY_RC(dev_alloc(c, &c->xgran, sizeof(unsigned long long) * 64 * (size_t)ntc));
             VLGBA_CHECK(hipMemsetAsync(c->xgran, 0, sizeof(unsigned long long) * 64 * (size_t)ntc,
                                        d->stream));
             if (P.cr_fused) {
                 const size_t nfl = (size_t)5 * P.cr_nlev * ntc;
-                TRY_RC(dev_alloc(&c->crflag, sizeof(unsigned) * nfl));
+                TRY_RC(dev_alloc(c, &c->crflag, sizeof(unsigned) * nfl));
                 VLGBA_CHECK(hipMemsetAsync(c->crflag, 0, sizeof(unsigned) * nfl, d->stream));
             }
-            TRY_RC(dev_alloc(&c->crf, sizeof(int) * (P.frec.size() + 1)));
-            TRY_RC(dev_alloc(&c->crs, sizeof(int) * (P.srec.size() + 1)));
+            TRY_RC(dev_alloc(c, &c->crf, sizeof(int) * (P.frec.size() + 1)));
+            TRY_RC(dev_alloc(c, &c->crs, sizeof(int) * (P.srec.size() + 1)));
             TRY_RC(put(c->crf, P.frec));
             TRY_RC(put(c->crs, P.srec));
             VLGBA_CHECK(hipStreamSynchronize(d->stream));
         }
-        TRY_RC(dev_alloc(&c->cr_elim, sizeof(int) * P.elim.size()));
-        TRY_RC(dev_alloc(&c->cr_keep, sizeof(int) * (P.keep.size() + 1)));
-        TRY_RC(dev_alloc(&c->crL, sizeof(double) * 2 * (size_t)ntc *
+        TRY_RC(dev_alloc(c, &c->cr_elim, sizeof(int) * P.elim.size()));
+        TRY_RC(dev_alloc(c, &c->cr_keep, sizeof(int) * (P.keep.size() + 1)));
+        TRY_RC(dev_alloc(c, &c->crL, sizeof(double) * 2 * (size_t)ntc *
                                       (P.cr32 ? T32 * T32 : NB * NB)));
         TRY_RC(put(c->cr_elim, P.elim));
         TRY_RC(put(c->cr_keep, P.keep));
     }
     // per envelope tile: the co-visible blocks (j >= k) overlapping it
-    TRY_RC(dev_alloc(&c->tb_ptr, sizeof(int) * P.tptr.size()));
-    TRY_RC(dev_alloc(&c->tb_blk, sizeof(int) * (P.tblk.size() + 1)));
+    TRY_RC(dev_alloc(c, &c->tb_ptr, sizeof(int) * P.tptr.size()));
+    TRY_RC(dev_alloc(c, &c->tb_blk, sizeof(int) * (P.tblk.size() + 1)));
     TRY_RC(put(c->tb_ptr, P.tptr));
     TRY_RC(put(c->tb_blk, P.tblk));
     VLGBA_CHECK(hipStreamSynchronize(d->stream));
@@ -2349,12 +2352,12 @@ int ba_chol_setup(ba_dev *d, const int *blk_jk, int nb)
     // inverses, the forward-solve result (+ the 32-row CR's last tile)
     const bool nd = P.nd_np > 0;
     const long long sdim = nd ? P.slds : d->lds;
-    TRY_RC(dev_alloc(&c->S, sizeof(double) * (size_t)(sdim * sdim)));
-    TRY_RC(dev_alloc(&c->linv, sizeof(double) * (size_t)(sdim / NB) * NB * NB));
-    TRY_RC(dev_alloc(&c->ywork, sizeof(double) * (size_t)(sdim + NB)));
+    TRY_RC(dev_alloc(c, &c->S, sizeof(double) * (size_t)(sdim * sdim)));
+    TRY_RC(dev_alloc(c, &c->linv, sizeof(double) * (size_t)(sdim / NB) * NB * NB));
+    TRY_RC(dev_alloc(c, &c->ywork, sizeof(double) * (size_t)(sdim + NB)));
     if (nd) {
         auto up = [&](int **dst, const std::vector<int> &v) -> int {
-            TRY_RC(dev_alloc(dst, sizeof(int) * (v.size() + 1)));
+            TRY_RC(dev_alloc(c, dst, sizeof(int) * (v.size() + 1)));
             return put(*dst, v);
         };
         TRY_RC(up(&c->nd_crow, P.crow));
@@ -2364,32 +2367,32 @@ int ba_chol_setup(ba_dev *d, const int *blk_jk, int nb)
         TRY_RC(up(&c->nd_pptr, P.pptr));
         TRY_RC(up(&c->nd_rec, P.rec));
         TRY_RC(up(&c->nd_klist, P.klist));
-        TRY_RC(dev_alloc(&c->nd_rhs, sizeof(double) * (size_t)P.slds));
-        TRY_RC(dev_alloc(&c->nd_x, sizeof(double) * (size_t)P.slds));
-        TRY_RC(dev_alloc(&c->nd_part, sizeof(double) * ((size_t)P.nd_nrec + 1) * (NB * NB + NB)));
+        TRY_RC(dev_alloc(c, &c->nd_rhs, sizeof(double) * (size_t)P.slds));
+        TRY_RC(dev_alloc(c, &c->nd_x, sizeof(double) * (size_t)P.slds));
+        TRY_RC(dev_alloc(c, &c->nd_part, sizeof(double) * ((size_t)P.nd_nrec + 1) * (NB * NB + NB)));
         VLGBA_CHECK(hipStreamSynchronize(d->stream));
     }
-    TRY_RC(dev_alloc(&c->pan_list, sizeof(int) * (P.pan_list.size() + 1)));
+    TRY_RC(dev_alloc(c, &c->pan_list, sizeof(int) * (P.pan_list.size() + 1)));
     if (P.back_one_launch) {
-        TRY_RC(dev_alloc(&c->pan_ptr, sizeof(int) * (nt + 1)));
+        TRY_RC(dev_alloc(c, &c->pan_ptr, sizeof(int) * (nt + 1)));
         TRY_RC(put(c->pan_ptr, P.pan_ptr));
-        TRY_RC(dev_alloc(&c->xgran64, sizeof(unsigned long long) * 128 * (size_t)nt));
+        TRY_RC(dev_alloc(c, &c->xgran64, sizeof(unsigned long long) * 128 * (size_t)nt));
         VLGBA_CHECK(hipMemsetAsync(c->xgran64, 0, sizeof(unsigned long long) * 128 * (size_t)nt,
                                    d->stream));
     }
     if (P.handoff) {   // the factor's in-launch hand-off
-        TRY_RC(dev_alloc(&c->kflag, sizeof(unsigned) * (size_t)nt));
+        TRY_RC(dev_alloc(c, &c->kflag, sizeof(unsigned) * (size_t)nt));
         VLGBA_CHECK(hipMemsetAsync(c->kflag, 0, sizeof(unsigned) * (size_t)nt, d->stream));
         // runner mode's flags: lflag | dflag | uflag | pflag, nt each, then
         // the runner's timeout word.  Opt-in (VLGBA_ENV_RUNNER=1): the runner
         // makes progress only while its stream has a hardware queue of its own
         if (P.runner_flags) {
             const size_t nw = 4 * (size_t)nt + 1;
-            TRY_RC(dev_alloc(&c->rflag, sizeof(unsigned) * nw));
+            TRY_RC(dev_alloc(c, &c->rflag, sizeof(unsigned) * nw));
             VLGBA_CHECK(hipMemsetAsync(c->rflag, 0, sizeof(unsigned) * nw, d->stream));
         }
     }
-    TRY_RC(dev_alloc(&c->env_tiles, sizeof(int) * (P.env.size() + 1)));
+    TRY_RC(dev_alloc(c, &c->env_tiles, sizeof(int) * (P.env.size() + 1)));
     TRY_RC(put(c->pan_list, P.pan_list));
     VLGBA_CHECK(hipMemcpyAsync(c->env_tiles, P.env.data(), sizeof(int) * P.env.size(),
                                hipMemcpyHostToDevice, d->stream));

@@ -568,3 +568,62 @@ void chol_nd_step(const chol_plan &plan, int st, bool run, nd_step *Pout)
 }
 
 #pragma GCC visibility pop
+
+// ---- block-Jacobi PCG (ba_pcg.hip): S as a block CSR over both triangles ----
+#pragma GCC visibility push(hidden)
+
+int pcg_plan_build(int m, const int *blk_jk, int nb, pcg_plan &out)
+{
+    out = pcg_plan{};
+    if (m < 1 || nb < 0 || (nb > 0 && !blk_jk)) return -1;
+    out.rowptr.assign((size_t)m + 1, 0);
+    out.dblk.assign((size_t)m, -1);
+    for (int b = 0; b < nb; b++) {
+        const int j = blk_jk[2 * b], k = blk_jk[2 * b + 1];
+        if (j < k || k < 0 || j >= m) return -1;
+        out.rowptr[(size_t)j + 1]++;
+        if (j != k) out.rowptr[(size_t)k + 1]++;
+    }
+    for (int j = 0; j < m; j++) out.rowptr[(size_t)j + 1] += out.rowptr[j];
+    const int nnz = out.rowptr[m];
+    // (neighbour, block, transposed) per row, then each row by neighbour
+    struct ent_t {
+        int k, b, t;
+    };
+    std::vector<ent_t> e((size_t)nnz);
+    std::vector<int> fill(out.rowptr.begin(), out.rowptr.end() - 1);
+    for (int b = 0; b < nb; b++) {
+        const int j = blk_jk[2 * b], k = blk_jk[2 * b + 1];
+        e[(size_t)fill[j]++] = {k, b, 0};
+        if (j != k) e[(size_t)fill[k]++] = {j, b, 1};
+    }
+    out.ent.resize(2 * (size_t)nnz);
+    out.nbr.resize((size_t)nnz);
+    for (int j = 0; j < m; j++) {
+        const int e0 = out.rowptr[j], e1 = out.rowptr[(size_t)j + 1];
+        std::sort(e.begin() + e0, e.begin() + e1,
+                  [](const ent_t &x, const ent_t &y) { return x.k < y.k; });
+        for (int q = e0; q < e1; q++) {
+            if (q > e0 && e[q].k == e[(size_t)q - 1].k) return -1;   // a pair given twice
+            out.ent[2 * (size_t)q] = e[q].b;
+            out.ent[2 * (size_t)q + 1] = e[q].t;
+            out.nbr[q] = e[q].k;
+            if (e[q].k == j) out.dblk[j] = e[q].b;
+        }
+    }
+    return nnz;
+}
+
+#pragma GCC visibility pop
+
+extern "C" __attribute__((visibility("default"))) int
+vlgba_debug_pcg_plan(int m, const int *blk_jk, int nb, int *rowptr, int *ent)
+{
+    if (!rowptr || !ent) return -1;
+    pcg_plan P;
+    const int nnz = pcg_plan_build(m, blk_jk, nb, P);
+    if (nnz < 0) return -1;
+    std::copy(P.rowptr.begin(), P.rowptr.end(), rowptr);
+    std::copy(P.ent.begin(), P.ent.end(), ent);
+    return nnz;
+}

@@ -126,4 +126,21 @@ int chol_selinv_sources(const std::vector<int> &elim, const std::vector<int> &ep
 // Step st of the ND arcs' side-by-side factorization (run: the runner started)
 void chol_nd_step(const chol_plan &plan, int st, bool run, nd_step *P);
 
+// ---- the block-Jacobi PCG's structure (ba_pcg.hip) ---------------------------
+// S as a block CSR over both triangles, from the blocks the Schur phase stores
+// (j >= k only): row j lists its neighbour cameras k ascending, the diagonal
+// block among them, each as the block's index and whether the row reads it
+// transposed (S_jk = S_kj^T for j < k).  A camera without a block has an empty
+// row.
+struct pcg_plan {
+    std::vector<int> rowptr;   // [m + 1]
+    std::vector<int> ent;      // [nnz][2] (block, transposed)
+    std::vector<int> nbr;      // [nnz] the neighbour camera
+    std::vector<int> dblk;     // [m] the diagonal block of camera j, or -1
+};
+// A function of its arguments only.  Returns nnz, or -1 for a pair with j < k,
+// an index outside [0, m) or a pair given twice (vlgba_debug_pcg_plan is its
+// exported entry).
+int pcg_plan_build(int m, const int *blk_jk, int nb, pcg_plan &out);
+
 #pragma GCC visibility pop

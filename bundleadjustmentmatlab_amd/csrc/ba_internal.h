@@ -29,6 +29,7 @@
 #include "ba_limits.h"
 
 struct ba_chol;   // the reduced solve's state (ba_chol.h)
+struct ba_pcg;    // ... of the block-Jacobi PCG (ba_pcg.h)
 
 #define VLGBA_CHECK(x)                                                              \
     do {                                                                            \
@@ -126,9 +127,14 @@ struct ba_dev {
     // lists and flags of the method the plan chose.  Owned by ba_chol_setup /
     // ba_chol_free; null in stage-mode contexts (which solve nothing)
     ba_chol *chol;
+    // dense_solve = 5: block-Jacobi PCG on sblk / rhs themselves (ba_pcg.hip).
+    // Owned by ba_pcg_setup / ba_pcg_free; such a context has no chol (no dense
+    // S, no plan of the direct solves), every other context no pcg
+    ba_pcg *pcg;
     int dense_solve;   // 0 auto, 1: every lower tile (measurement), 2: envelope, no CR,
                        // 3: sequential Cholesky (parity mode), 4: nested dissection
-                       // whenever the cameras split (tests; 0 takes it when it pays)
+                       // whenever the cameras split (tests; 0 takes it when it pays),
+                       // 5: block-Jacobi PCG (opt-in)
     // the two decisions a pass takes from the plan (ctx_setup):
     // direct assembly (camera-aligned CR, one rank, fast path): k_schur_reduce
     // writes each block's lower entries straight into S (and the pinv rule
@@ -267,6 +273,17 @@ struct ba_dev {
 
 #define BA_PART_MAX 65536
 
+// CALL with NA a compile-time constant, for the camera models' sizes
+#define BA_DISPATCH(NAEXPR, CALL)                                                   \
+    switch (NAEXPR) {                                                               \
+    case 6: { constexpr int NA = 6; CALL; } break;                                  \
+    case 7: { constexpr int NA = 7; CALL; } break;                                  \
+    case BA_RAD_NA: { constexpr int NA = BA_RAD_NA; CALL; } break;                  \
+    case 10: { constexpr int NA = 10; CALL; } break;                                \
+    case BA_PROJ_NA: { constexpr int NA = BA_PROJ_NA; CALL; } break;                \
+    default: return -1000;                                                          \
+    }
+
 // ---- ba_kernels.hip ----
 int ba_launch_rotations(ba_dev *d, const double *a, double *rot);
 int ba_launch_linearize(ba_dev *d, ba_flags f);
@@ -388,6 +405,16 @@ int ba_cr32_selinv(ba_dev *d, const int *src, double *sig);
 // ascending, V column major ld x ld): MATLAB's tolerance ld * eps(max |ev|)
 int ba_pinv_apply(ba_dev *d, const double *V, const double *ev, long long ld, const double *rhs,
                   double *work, double *da);
+
+// ---- ba_pcg.hip (dense_solve = 5) ----
+// the block CSR over both triangles, the work vectors, M^-1 (d->pcg; d->da
+// must be allocated)
+int ba_pcg_setup(ba_dev *d, const int *blk_jk_host, int nb);
+void ba_pcg_free(ba_dev *d);
+// da = the PCG iterate for sblk / rhs as the Schur phase left them (rhs gets
+// its zeros on the exactly-zero rows); the status words scal[4] (failure) and
+// scal[5] (0); d->pcg's statistics.  Synchronises the stream once per batch
+int ba_pcg_solve(ba_dev *d);
 
 // ---- ba_cov.hip (vlgba_covariance) ----
 // track-length bins of k_point_cov: up to BA_COV_T8 views 8 lanes per point,

@@ -2730,16 +2730,6 @@ static inline int grid_for(long long work, int bs, int cap)
     return (int)g;
 }
 
-#define BA_DISPATCH(NAEXPR, CALL)                                                   \
-    switch (NAEXPR) {                                                               \
-    case 6: { constexpr int NA = 6; CALL; } break;                                  \
-    case 7: { constexpr int NA = 7; CALL; } break;                                  \
-    case BA_RAD_NA: { constexpr int NA = BA_RAD_NA; CALL; } break;                  \
-    case 10: { constexpr int NA = 10; CALL; } break;                                \
-    case BA_PROJ_NA: { constexpr int NA = BA_PROJ_NA; CALL; } break;                \
-    default: return -1000;                                                          \
-    }
-
 static const int PT_GRID_CAP = 8192;  // partial-sum slots used by per-point kernels
 
 int ba_launch_rotations(ba_dev *d, const double *a, double *rot)

@@ -16,6 +16,7 @@
 #include "ba_internal.h"
 #include "ba_plan.h"   // the host planner: sort_obs, order_points_by_kind, plan_host
 #include "ba_chol.h"   // the reduced solve's state and plan (ba_dev::chol)
+#include "ba_pcg.h"    // ... or the block-Jacobi PCG's (ba_dev::pcg)
 #include "../../include/vlgba.h"
 
 #include <rccl/rccl.h>
@@ -406,6 +407,7 @@ static void ctx_free(vlgba_ctx *c)
         delete c->d.kt;
     }
     ba_chol_free(&c->d);
+    ba_pcg_free(&c->d);
     if (c->comm) comm_release(c->comm);
     if (c->has_aux) aux_release(c->aux);
     delete c;
@@ -712,7 +714,15 @@ static int ctx_setup(vlgba_ctx *c, const vlgba_problem *p, const host_obs &h,
     // blocks | rhs | old SSE contiguous: one all-reduce per pass (world > 1)
     TRY(ctx_alloc(c, &d.sblk, (size_t)na * na * d.nb + d.lds + 1));
     d.rhs = d.sblk + (size_t)na * na * d.nb;
-    if (!stage_mode) {
+    if (!stage_mode && d.dense_solve == 5) {
+        // block-Jacobi PCG on sblk / rhs themselves: no dense S, no plan of the
+        // direct solves (d.chol stays null), no direct assembly, no folded
+        // camera update
+        TRY(ctx_alloc(c, &d.da, (size_t)d.lds));
+        ST_MARK("allocs");
+        TRY(ba_pcg_setup(&d, hb.jk.data(), d.nb));
+        ST_MARK("pcg_setup");
+    } else if (!stage_mode) {
         TRY(ctx_alloc(c, &d.da, (size_t)d.lds));   // S, linv, ywork: ba_chol_setup
         ST_MARK("allocs");
         TRY(ba_chol_setup(&d, hb.jk.data(), d.nb));
@@ -901,12 +911,14 @@ static int ctx_create(const vlgba_problem *p, const vlgba_options *o, vlgba_ctx 
         c->verbose = o->verbose;
         c->d.dense_solve = o->dense_solve;
         c->d.ordered = o->ordered != 0;
+        // the PCG (dense_solve = 5) is the fast path's: not with ordered / parity
+        if (o->dense_solve == 5 && (o->ordered != 0 || stage_mode)) { rc = VLGBA_E_ARG; break; }
         if (o->ordered == 2) {   // parity mode: + sequential solve and LM scalars
             if (c->world > 1) { rc = VLGBA_E_ARG; break; }
             c->d.parity = 1;
             c->d.dense_solve = 3;
         } else if (o->ordered < 0 || o->ordered > 2 || o->dense_solve < 0 ||
-                   o->dense_solve > 4) {
+                   o->dense_solve > 5) {
             rc = VLGBA_E_ARG;
             break;
         }
@@ -941,6 +953,7 @@ static int ctx_create(const vlgba_problem *p, const vlgba_options *o, vlgba_ctx 
         if (rc) break;
         // ... so a problem the planner hands to the ordered kernels is refused
         if (p->num_a == BA_RAD_NA && c->d.ordered) { rc = VLGBA_E_ARG; break; }
+        if (c->d.pcg && c->d.ordered) { rc = VLGBA_E_ARG; break; }   // (the PCG likewise)
         ST_MARK("setup_end");
         if (c->d.parity) {   // new projections for the sequential new-SSE sum
             rc = ctx_alloc(c, &c->d.xh_out, 2 * (size_t)c->d.N + 2);
@@ -1113,6 +1126,23 @@ static int recovery_update(vlgba_ctx *c, double lam, double hs[6])
     return collect_scalars(c, false, false, hs);
 }
 
+// The reduced solve of a pass, whichever the context has: the block-Jacobi PCG
+// on the blocks themselves (it assembles nothing and never forms a_new), or
+// the assembly of S and the direct solve the plan chose.  pass: lm_pass's own
+// call, which marks the end of the assembly phase (event 5)
+static int reduced_solve(vlgba_ctx *c, bool *cam_updated, int nospin, bool pass)
+{
+    ba_dev &d = c->d;
+    *cam_updated = false;
+    if (d.pcg) {
+        if (pass) mark(c, 5);
+        return ba_pcg_solve(&d);
+    }
+    TRY(ba_launch_assemble(&d));
+    if (pass) mark(c, 5);
+    return ba_chol_solve(&d, cam_updated, nospin);
+}
+
 // A hand-off spin of the one-launch solve gave up (timeout word scal[5]):
 // nothing is wrong with S, the launch just did not finish in time.  Re-form
 // S and e_ (the solve works in place), solve with the launches that never
@@ -1123,11 +1153,12 @@ static int resolve_nospin(vlgba_ctx *c, double lam, double hs[6])
 {
     ba_dev &d = c->d;
     TRY(schur_phase(c, lam));
-    TRY(ba_launch_assemble(&d));
-    bool cam_updated = false;   // (never set by a solve without spins)
-    TRY(ba_chol_solve(&d, &cam_updated, 1));
+    // (a solve without spins never sets it; a PCG context solves again the same way)
+    bool cam_updated = false;
+    TRY(reduced_solve(c, &cam_updated, 1, false));
     TRY(recovery_update(c, lam, hs));
     c->spin_retries++;
+    if (!d.chol) return 0;
     // one of the envelope runner's own hand-offs gave up (most likely its side
     // stream sharing a hardware queue with the library stream, so the column
     // launches queue behind it): this context's column launches alone from now on
@@ -1322,10 +1353,8 @@ static int lm_pass(vlgba_ctx *c, int relinearize, vlgba_step_info *info)
     TRY(stage1(c, relinearize, route, &left));
     TRY(schur_phase(c, lam, left));
     mark(c, 4);
-    TRY(ba_launch_assemble(&d));
-    mark(c, 5);
     bool cam_updated = false;   // the solve formed a_new / rot_new (one-launch CR)
-    TRY(ba_chol_solve(&d, &cam_updated));
+    TRY(reduced_solve(c, &cam_updated, 0, true));
     for (int w = 4; w <= 5; w++) {   // test hooks: as if a pivot failed / a spin gave up
         int &k = w == 4 ? c->debug_pivots : c->debug_timeouts;
         if (k > 0) {
@@ -1355,8 +1384,9 @@ static int lm_pass(vlgba_ctx *c, int relinearize, vlgba_step_info *info)
         TRY(resolve_nospin(c, lam, hs));
         info->spin_retry = 1;
     }
-    if (hs[4] != 0.0 && d.chol->plan.nd_np > 0) {   // the nested-dissection order's pivot: the
-        const int rc = nd_natural_retry(c, lam, hs);   // natural order first
+    // the nested-dissection order's pivot: the natural order first
+    if (hs[4] != 0.0 && d.chol && d.chol->plan.nd_np > 0) {
+        const int rc = nd_natural_retry(c, lam, hs);
         if (rc < 0) return rc;
         info->nd_retry = 1;
         if (rc == 0) hs[4] = 0.0;
@@ -1380,8 +1410,8 @@ static int lm_pass(vlgba_ctx *c, int relinearize, vlgba_step_info *info)
             kt->ms[kt->kid[q / 2]] += ms;
             kt->calls[kt->kid[q / 2]]++;
         }
-        if (kt) {
-            kt->nev = 0;
+        if (kt) kt->nev = 0;
+        if (kt && d.chol) {
             // the solve's algorithmic flops (chol_plan_build's count) on the timers
             // that ran them: one-launch / per-level CR, or the envelope's steps,
             // separator SYRK and backward solve
@@ -2059,6 +2089,34 @@ int vlgba_debug_force_status(vlgba_ctx *c, int word, int passes)
     return 0;
 }
 
+int vlgba_set_pcg(vlgba_ctx *c, double tol, int max_iter)
+{
+    if (!c || !c->d.pcg || !std::isfinite(tol) || tol >= 1.0) return VLGBA_E_ARG;
+    if (tol > 0.0) c->d.pcg->tol = tol;
+    if (max_iter > 0) c->d.pcg->max_iter = max_iter;
+    return 0;
+}
+
+int vlgba_get_pcg(vlgba_ctx *c, double *tol, int *max_iter)
+{
+    if (!c || !c->d.pcg) return VLGBA_E_ARG;
+    if (tol) *tol = c->d.pcg->tol;
+    if (max_iter) *max_iter = c->d.pcg->max_iter;
+    return 0;
+}
+
+int vlgba_get_pcg_stats(vlgba_ctx *c, int *iterations, double *relres, int *converged,
+                        long long *total)
+{
+    if (!c || !c->d.pcg) return VLGBA_E_ARG;
+    const ba_pcg &P = *c->d.pcg;
+    if (iterations) *iterations = P.iters;
+    if (relres) *relres = P.relres;
+    if (converged) *converged = P.conv;
+    if (total) *total = P.total;
+    return 0;
+}
+
 int vlgba_set_timing(vlgba_ctx *c, int on)
 {
     if (!c) return VLGBA_E_ARG;
@@ -2159,7 +2217,8 @@ int vlgba_plan_info(vlgba_ctx *c, long long *info, int len)
                                       P.nd_np ? P.nt - P.nd_a0[P.nd_np] : 0,
                                       (long long)P.fl_factor, (long long)P.fl_syrk,
                                       (long long)P.fl_back, d.chol ? d.chol->runner_runs : 0,
-                                      d.vinv_fold, d.camupd_fold};
+                                      d.vinv_fold, d.camupd_fold, d.pcg ? 1 : 0,
+                                      d.pcg ? d.pcg->bytes : d.chol ? d.chol->bytes : 0};
     for (int k = 0; k < len && k < VLGBA_NPLAN; k++) info[k] = v[k];
     return VLGBA_NPLAN;
 }

@@ -48,7 +48,10 @@ extern "C" {
  * entry point changed) and the batched per-point entries (vlgba_triangulate,
  * vlgba_intersect: entry points only) and their counterparts with a model, a
  * Jacobian mode and a loss (vlgba_resect_ex, vlgba_intersect_ex,
- * vlgba_triangulate_ex: likewise).  Callers
+ * vlgba_triangulate_ex: likewise) and the block-Jacobi PCG reduced solve
+ * (dense_solve = 5, a value vlgba_create refused before; vlgba_set_pcg,
+ * vlgba_get_pcg, vlgba_get_pcg_stats, vlgba_debug_pcg_plan: entry points only;
+ * VLGBA_NPLAN 33).  Callers
  * check it once at load time with VLGBA_ABI_CHECK() (the MEX gateways and the Python
  * loader do): the library compares the version and the struct sizes the
  * caller was compiled with against its own and returns 0 or VLGBA_E_ABI. */
@@ -133,8 +136,17 @@ typedef struct {
  * 4: the envelope Cholesky on a nested-dissection camera order whenever the
  *   cameras split into independent arcs + a separator (0 takes that order
  *   when it shortens the chain of factor steps by a quarter or more).
-     * Any of them meeting a non-positive pivot falls back to pinv(S) e_ from
-     * a symmetric eigen-decomposition on the GPU (vlgba_step_info.pinv)      */
+     * 5: block-Jacobi preconditioned conjugate gradients on the co-visible
+     *   blocks themselves (opt-in; no dense S is allocated: device memory
+     *   linear in the blocks and cameras).  An inexact step: the iteration
+     *   stops at sqrt(r'M^-1 r / e_'M^-1 e_) <= tol or at the iteration limit
+     *   (vlgba_set_pcg), and the iterate is the step either way.  Fast path
+     *   only: VLGBA_E_ARG with ordered != 0 and on a problem the planner
+     *   hands to the ordered kernels.
+     * Any of them meeting a non-positive pivot (5: in a camera's diagonal
+     * block, or p'Sp <= 0, or a scalar that is not finite) falls back to
+     * pinv(S) e_ from a symmetric eigen-decomposition on the GPU
+     * (vlgba_step_info.pinv)                                                 */
     int dense_solve;
     /* 1: "ordered" mode -- every sum over points runs sequentially in
      * ascending point order exactly as the reference loops do, making the
@@ -414,6 +426,23 @@ int vlgba_get_loss(vlgba_ctx *ctx, int *kind, double *scale);
 #define VLGBA_JAC_ANALYTIC 1
 int vlgba_set_jacobian(vlgba_ctx *ctx, int kind);
 int vlgba_get_jacobian(vlgba_ctx *ctx, int *kind);
+/* ---- the block-Jacobi PCG reduced solve (vlgba_options.dense_solve = 5) ----
+ * Preconditioned conjugate gradients on S da = e_ from da = 0, M_j the diagonal
+ * block of camera j; after iteration k the solve stops when sqrt(rz_k / rz_0)
+ * <= tol (rz = r'M^-1 r) or k == max_iter, and the iterate is the step (every
+ * CG iterate from zero is a descent direction of the damped model).  A row
+ * whose diagonal entry is exactly 0 (a pivot camera, fix_motion, a camera
+ * without observations) gets a unit diagonal and a zero right-hand side: da is
+ * exactly 0 there.  Deterministic: two calls on the same state give the same
+ * bits and the same iteration count, on every rank of a sharded context.
+ * tol <= 0 or max_iter <= 0 keeps the current value; VLGBA_E_ARG for a non-finite tol,
+ * tol >= 1, and a context whose solver is not the PCG.  Defaults: tol 0.1, max_iter 500. */
+int vlgba_set_pcg(vlgba_ctx *ctx, double tol, int max_iter);
+int vlgba_get_pcg(vlgba_ctx *ctx, double *tol, int *max_iter);
+/* the last pass's solve: iterations run, sqrt(rz_k / rz_0) at its end, 1 when the tolerance
+ * was met; total: iterations summed over the context's passes (any pointer may be NULL) */
+int vlgba_get_pcg_stats(vlgba_ctx *ctx, int *iterations, double *relres, int *converged,
+                        long long *total);
 /* per observation of this rank at the context's current parameters, in the
  * order of vlgba_get_linearization's W rows (point-major, cameras ascending
  * within a point): e [2 x N_local] the unweighted residuals x - x_hat, w
@@ -465,10 +494,19 @@ const char *vlgba_kernel_name(int k);
  * k_point_vinv launch; VLGBA_VINV_FOLD=0 or a plan whose MFMA groups do not
  * tile every point: 0) [30] 1: the one-launch cyclic reduction does the camera
  * update (no k_camera_update launch after it; VLGBA_CAMUPD_FOLD=0 or another
- * solver: 0).  Writes min(len, VLGBA_NPLAN) entries, returns
+ * solver: 0) [31] 1: the reduced solve is the block-Jacobi PCG (dense_solve =
+ * 5; [11]-[14], [19] and [23]-[28] are then 0) [32] bytes of device memory the
+ * reduced solve itself holds, without the blocks and e_ every solver has: for
+ * the direct solvers the dense S, the tile inverses and the lists of the
+ * chosen method (>= 8 lds^2, lds = NA * cameras rounded up to 64); for the
+ * PCG, with ld = [3] * [2], m = [2], nb = [10],
+ *   8 (4 + NA) ld + ld + 16 ceil(m / 4) + 64 + 8 m + 4 + 24 nb
+ * (r, z, p, q; the M_j^-1 blocks; the zero-row mask; the dot products'
+ * partial sums; the state words; the block CSR over both triangles with room
+ * for 2 nb entries): no ld^2 term.  Writes min(len, VLGBA_NPLAN) entries, returns
  * VLGBA_NPLAN (a caller built for fewer entries keeps working: entries are
  * only ever appended, without an ABI bump). */
-#define VLGBA_NPLAN 31
+#define VLGBA_NPLAN 33
 int vlgba_plan_info(vlgba_ctx *ctx, long long *info, int len);
 
 /* ---- stage entries with the reference MEX argument layouts ---------------
@@ -714,6 +752,15 @@ int vlgba_debug_nd_plan(int m, int num_a, const int *blk_jk, int nb, int *bnd, i
  * stored); -1, 0 where p or q is absent.  Returns the level count, -1 on bad
  * arguments. */
 int vlgba_debug_selinv_plan(int ntiles, int *elim, int *eptr, int *src);
+/* The block-Jacobi PCG's structure on the host (no GPU): the reduced system of
+ * m cameras as a block CSR over both triangles, from the co-visible blocks
+ * blk_jk [2 * nb] (j >= k).  Row j (rowptr [m + 1]) lists its neighbour
+ * cameras ascending, the diagonal block among them; entry e is ent[2 e] the
+ * block's index and ent[2 e + 1] = 1 when the row reads it transposed (the
+ * neighbour is the block's j).  ent must hold 2 * (2 nb) ints.  Returns the
+ * entry count nnz, -1 on bad arguments (a pair with j < k, an index outside
+ * [0, m), a pair given twice). */
+int vlgba_debug_pcg_plan(int m, const int *blk_jk, int nb, int *rowptr, int *ent);
 
 /* Library / device info: writes a NUL-terminated string, returns its length. */
 int vlgba_version(char *buf, int len);
