@@ -308,9 +308,9 @@ int ba_launch_yeb(ba_dev *d);
 // (unweighted), w [N], rho [N] of the context's loss; any pointer may be NULL
 int ba_launch_obs_residuals(ba_dev *d, double *e, double *w, double *rho);
 int ba_launch_publish(ba_dev *d);   // scal[0..5] + ++seq -> hres (host-mapped)
-void *ba_dmalloc(size_t bytes);   // per-device caching allocator (ba_solver.cpp)
+void *ba_dmalloc(size_t bytes);   // per-device caching allocator (ba_runtime.cpp)
 // raise kernel fn's dynamic-LDS limit to >= bytes on the current device (cached
-// per (kernel, device), thread-safe; ba_solver.cpp)
+// per (kernel, device), thread-safe; ba_runtime.cpp)
 int ba_ensure_dyn_lds(const void *fn, size_t bytes);
 void ba_dfree(void *p);
 // Typed device memory on that allocator and the asynchronous copies on a

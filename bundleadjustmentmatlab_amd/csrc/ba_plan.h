@@ -3,8 +3,8 @@
 // plan of the fast Schur path (ba_plan.cpp).  Host only: no HIP, RCCL or
 // rocSOLVER header, so the planner builds with any C++17 compiler
 // (tools/bench_plan.cpp hashes its plans, tests/test_plan_sanitize.py runs it
-// under the sanitizers).  ba_solver.cpp's ctx_create / ctx_setup call it and
-// upload what it returns.
+// under the sanitizers).  ba_solver.cpp's ctx_create / ctx_setup (and the
+// setup_* pieces of the latter) call it and upload what it returns.
 #pragma once
 #include "ba_limits.h"
 #include "../../include/vlgba.h"

@@ -23,7 +23,7 @@ def unique_id_bytes() -> bytes:
 
 
 def shard_points(pt_ptr: np.ndarray, world: int, rank: int) -> tuple[int, int]:
-    """[p0, p1) of rank: same rule as ctx_create in ba_solver.cpp (lower_bound of
+    """[p0, p1) of rank: same rule as ctx_ranks in ba_solver.cpp (lower_bound of
     N*r/world in the point offsets)."""
     n = len(pt_ptr) - 1
     N = int(pt_ptr[-1])

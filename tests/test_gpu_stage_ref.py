@@ -173,7 +173,7 @@ def _case(scene, na=6, lam=1e-3, env=None, plan=None, fixed=(), launches=None, *
 # launches no k_assemble; the one-launch CR is one k_cr_factor, the per-level
 # CR one per level.  (k_schur_long_acc has no timer of its own -- it runs
 # inside k_schur_reduce's -- so VLGBA_LONG_ACC's two routes are told apart
-# only by the variable itself, spelt as ba_solver.cpp reads it.)
+# only by the variable itself, spelt as ba_solver.cpp's setup_long_pairs reads it.)
 _ONE = lambda n: n == 1          # noqa: E731
 _NONE = lambda n: n == 0         # noqa: E731
 _MANY = lambda n: n > 1          # noqa: E731
@@ -399,7 +399,7 @@ def test_update_stage(gpu, key):
     _facts(r, key)
     na, L = r["na"], r["lin"]
     # (the radial camera's back substitution takes all nine rows of da under
-    # either semantics: ba_solver.cpp, ndb of the radial model)
+    # either semantics: ba_solver.cpp's ctx_options, ndb of the radial model)
     ndb = na if r["kw"].get("semantics") == "nomex" or na == 9 else 6
     Vinv = sr.vinv_of(L["V"], r["lam"])
     ref, bound = sr.back_subst(na, ndb, r["pt"], r["cam"], L["W"], Vinv, L["eB"], r["da"])
